@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark: env-steps/s of the Skillshot step kernels on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 65536]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 65536] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs and no more: set-up, W warm-up
+ticks, the K timed ticks, the result line (and, with --dump-outputs DIR, what
+the timed path computed in its last tick as DIR/<name>.npy: dump_outputs).
+Every other leg named below (step_variants, full_contract_tick,
+rollout_random, large_batch, weak_scaling, learner, cpu_baseline) runs only
+with --full; the --no-* options then leave single legs out.
 
 Workload (BASELINE.json metric "env-steps/sec (whole node) at 65536 self-play
 envs; 1/2/4/8 GPU scaling", SURVEY.md §8(d) config 2 at the metric's size and
@@ -88,7 +95,45 @@ def parse():
     p.add_argument("--ticks-per-launch", type=int, default=400,
                    help="k_step_multi: ticks per launch (the headline runs K ticks in ceil(K / this) launches)")
     p.add_argument("--no-variants", action="store_true", help="skip the per-tick-launch / L2-resident legs")
+    p.add_argument("--full", action="store_true",
+                   help="also run every leg beside the headline (step variants, full contract, rollout, large batch, "
+                        "weak scaling, learner, CPU baseline); the --no-* options leave single legs out")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the headline path computed in its last step as DIR/<name>.npy")
     return p.parse_args()
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, env, rank=0, seed=0, budget=DUMP_BYTES):
+    """What a caller of the headline path (sk_env_step_multi on `env`) holds
+    after the last timed tick, as `path`/<name>.npy (ranks > 0:
+    <name>.rank<r>.npy): `done` u8[n] of that tick as float32, the state
+    planes the launch updated in place (pos, rot, qpos, qrot, qcdage, misc:
+    [n, w], int32 or f64) as float64, which holds both exactly, the RNG
+    `step_counter` and the episode `counters` (dones, hits_p1, hits_p2,
+    ticks_sum) as float64.  Past `budget` bytes in all, the per-game arrays
+    keep a fixed seeded sample of the games, whose ids are `games`.  Call
+    after the timed region's synchronize."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    st = env.state_dict()
+    per_game = {"done": env.bench_done.cpu().numpy().astype(np.float32)}
+    per_game.update((k, np.asarray(v).astype(np.float64)) for k, v in st.items() if k != "step_counter")
+    c = env.counters(stream=ctypes.c_void_p(env.bench_stream.cuda_stream))
+    out = {"step_counter": np.array([st["step_counter"]], dtype=np.float64),
+           "counters": np.array([c["dones"], c["hits_p1"], c["hits_p2"], c["ticks_sum"]], dtype=np.float64)}
+    n = env.n
+    row_bytes = sum(a.nbytes // n for a in per_game.values()) + 8  # + the id in `games`
+    keep = (budget - sum(a.nbytes for a in out.values())) // row_bytes
+    if keep < n:
+        games = np.sort(np.random.default_rng(seed).choice(n, size=keep, replace=False))
+        per_game = {k: a[games] for k, a in per_game.items()}
+        out["games"] = games.astype(np.float64)
+    out.update(per_game)
+    for k, a in out.items():
+        np.save(os.path.join(path, f"{k}.npy" if rank == 0 else f"{k}.rank{rank}.npy"), a)
 
 
 class TickGraphs:
@@ -382,6 +427,7 @@ def timed_multi(dev, n, seed, env_offset, tick_limit, k, warmup, ring, world, pe
         el = float(tt.item())
     env.bench_actions = acts
     env.bench_stream = st
+    env.bench_done = done  # the last tick's (dump_outputs)
     return el, e0.elapsed_time(e1), env
 
 
@@ -1009,7 +1055,10 @@ def main():
     if args.leg_child:
         leg_child_main(args, json.loads(args.leg_child))
         return
-    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if not args.full:  # a plain run: the headline alone
+        args.no_variants = args.no_rollout = args.no_full = args.no_large = args.no_weak = True
+        args.no_learner = args.no_cpu_baseline = True
+    world =int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if world > 1:
@@ -1041,6 +1090,8 @@ def main():
                                       per_launch=args.ticks_per_launch)
     value = n * world * K / elapsed
     counters = env.counters(stream=ctypes.c_void_p(env.bench_stream.cuda_stream))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, env, rank=rank, budget=DUMP_BYTES // world)
     env.close()
 
     # ---- roofline: the timed region is ceil(K / ticks_per_launch) back-to-back

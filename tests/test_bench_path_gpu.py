@@ -73,3 +73,47 @@ def test_bench_headline_path_equals_cpu_backend(bench_mod, kind):
     # episodes ended inside the counted launches only, and many crossed the limit
     assert counters["dones"] > n // 4 and counters["hits_p1"] + counters["hits_p2"] < counters["dones"]
     env.close()
+
+
+def test_dump_outputs_is_the_last_ticks_result(bench_mod, tmp_path):
+    """bench.py --dump-outputs: the files hold what the headline path computed
+    in its last timed tick (done of that tick, the state it left, the RNG step
+    counter, the episode counters), exactly (float64 holds the int32 planes
+    and the f64 rotations; done is 0 / 1), equal to the CPU backend's replay
+    of the same launches, and a second run from the same arguments writes the
+    same bytes.  1,000 games (no multiple of the 64-lane wave or the block),
+    tick limit 30 so that episodes end and restart within the 65 ticks."""
+    import skillshot_learning_amd as ssa
+    dev = torch.device("cuda", 0)
+    n, seed, limit, K, W, ring = 1000, 3, 30, 60, 5, 16
+    runs = []
+    for r in range(2):
+        trace = []
+        el, ev, env = bench_mod.timed_multi(dev, n, seed, 0, limit, K, W, ring, 1, per_launch=25, trace=trace)
+        bench_mod.dump_outputs(str(tmp_path / f"d{r}"), env)
+        runs.append((trace, env.bench_actions.cpu(), env.counters()))
+        env.close()
+    names = sorted(os.listdir(tmp_path / "d0"))
+    assert names == sorted(f"{k}.npy" for k in ("done", "pos", "rot", "qpos", "qrot", "qcdage", "misc",
+                                                 "step_counter", "counters"))
+    got = {f[:-4]: np.load(tmp_path / "d0" / f) for f in names}
+    for f in names:
+        assert (tmp_path / "d0" / f).read_bytes() == (tmp_path / "d1" / f).read_bytes(), f
+    assert got["done"].dtype == np.float32 and all(got[k].dtype == np.float64 for k in got if k != "done")
+    assert sum(a.nbytes for a in got.values()) <= bench_mod.DUMP_BYTES
+    trace, acts, counters = runs[0]
+    c = ssa.VecSkillshotGame(n, device="cpu", seed=seed, tick_limit=limit)
+    c.reset(random_positions=True)
+    done = None
+    for ev in trace:
+        if ev[0] == "clear":
+            c.clear_counters()
+        else:
+            done, _ = c.step_multi(acts, n_ticks=ev[2], slab0=ev[1])
+    want = c.state_dict()
+    assert got["step_counter"].tolist() == [want.pop("step_counter")]
+    for k, v in want.items():
+        assert got[k].shape == np.asarray(v).shape and np.array_equal(got[k], np.asarray(v)), k
+    assert np.array_equal(got["done"], done.cpu().numpy()) and set(np.unique(got["done"])) <= {0.0, 1.0}
+    assert got["counters"].tolist() == [counters[k] for k in ("dones", "hits_p1", "hits_p2", "ticks_sum")]
+    assert counters == c.counters() and counters["dones"] > n

@@ -13,8 +13,9 @@
 #   prof       rocprofv3 --kernel-trace --stats of the headline leg, K = 4,000 and the driver's K = 20
 #   proffull   rocprofv3 --kernel-trace --stats of the headline and full-contract legs (K = 4,000)
 #   proflearn  rocprofv3 kernel stats of the learner ticks (config 3 / 5, fp32 / bf16)
-#   bench      python bench.py (every leg)                        -> $O/bench_default.json
-#   bench20    python bench.py --steps 20 --warmup 5 (the driver)  -> $O/bench_driver_k20.json
+#   bench      python bench.py --full (every leg)                 -> $O/bench_default.json
+#   bench20    python bench.py --steps 20 --warmup 5 (the driver's plain run: the headline alone;
+#              BENCH_ARGS=--full for every leg)                   -> $O/bench_driver_k20.json
 #   pmclearn   PMC MFMA utilisation of the learner kernels
 #   pmcact     PMC MFMA / VALU / wait counters of the acting launch (tools/pmc_act_step.sh)
 #   pmcobs     SQ counters of the full-contract and headline multi-tick kernels (tools/pmc_multi_obs.sh)
@@ -76,7 +77,7 @@ for s in "${S[@]}"; do
     summ prof_bench prof_bench_k20;;
   proffull)
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_full -o prof -- python3 bench.py \
-      --no-learner --no-cpu-baseline --no-large --no-rollout --no-variants > $O/prof_full_bench.json \
+      --full --no-learner --no-cpu-baseline --no-large --no-rollout --no-variants > $O/prof_full_bench.json \
       2> $O/prof_full_bench.err || stop proffull $?
     summ prof_full_bench;;
   proflearn)
@@ -89,7 +90,7 @@ r = bench.learner_rate($n, 1, 0, 200, batch=256, exploration='$ex', precision='$
 print(json.dumps(r))" > $O/prof_learn_${tg}_$pr.json 2> $O/prof_learn_${tg}_$pr.err || stop proflearn $?
     done;;
   bench)
-    timeout -k 10 900 python3 -u bench.py ${BENCH_ARGS:-} > $O/bench_default.json 2> $O/bench_default.err || stop bench $?
+    timeout -k 10 900 python3 -u bench.py --full ${BENCH_ARGS:-} > $O/bench_default.json 2> $O/bench_default.err || stop bench $?
     summ bench_default;;
   bench20)
     timeout -k 10 400 python3 -u bench.py --steps 20 --warmup 5 ${BENCH_ARGS:-} > $O/bench_driver_k20.json \
