@@ -12,7 +12,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 LIB_DIR = os.path.join(HERE, "lib")
-# SK_LIB_PATH: load a prebuilt variant instead (A/B experiments, tools/gpu_lib_ab.sh)
+# SK_LIB_PATH: load a prebuilt variant instead (A/B experiments: tools/build_variant.sh,
+# tools/build_rev.sh)
 LIB_PATH = os.environ.get("SK_LIB_PATH") or os.path.join(LIB_DIR, "libskillshot.so")
 # csrc/sk_diag.hip (measurement-only kernels: the copy floor) is not part of
 # the product library: tools/build_variant.sh builds it into diagnostic

@@ -103,12 +103,6 @@ typedef int skv2i __attribute__((ext_vector_type(2)));
 typedef double skv2d __attribute__((ext_vector_type(2)));
 typedef float skv2f __attribute__((ext_vector_type(2)));
 
-#ifdef SK_STATE_NT
-#define SK_STATE_LD "nt"
-#else
-#define SK_STATE_LD ""
-#endif
-
 struct StepLoads {  // native vector types: inline asm cannot bind HIP's struct vectors
   skv2d r, qr;
   skv4i p, q, ca;
@@ -123,12 +117,12 @@ __device__ __forceinline__ void issue_step_loads(const View& v, const float2* ac
   skv2i m;
   skv2f a0, a1;
   asm volatile(
-      "global_load_dwordx4 %0, %8, off " SK_STATE_LD "\n\t"
-      "global_load_dwordx4 %1, %9, off " SK_STATE_LD "\n\t"
-      "global_load_dwordx4 %2, %10, off " SK_STATE_LD "\n\t"
-      "global_load_dwordx2 %3, %11, off " SK_STATE_LD "\n\t"
-      "global_load_dwordx4 %4, %12, off " SK_STATE_LD "\n\t"
-      "global_load_dwordx4 %5, %13, off " SK_STATE_LD "\n\t"
+      "global_load_dwordx4 %0, %8, off \n\t"
+      "global_load_dwordx4 %1, %9, off \n\t"
+      "global_load_dwordx4 %2, %10, off \n\t"
+      "global_load_dwordx2 %3, %11, off \n\t"
+      "global_load_dwordx4 %4, %12, off \n\t"
+      "global_load_dwordx4 %5, %13, off \n\t"
       "global_load_dwordx2 %6, %14, off nt\n\t"
       "global_load_dwordx2 %7, %15, off nt"
       : "=&v"(r), "=&v"(qr), "=&v"(ca), "=&v"(m), "=&v"(p), "=&v"(q), "=&v"(a0), "=&v"(a1)
@@ -168,25 +162,12 @@ __device__ __forceinline__ EnvRaw step_loads_env(const StepLoads& L) {
 __device__ __forceinline__ void store_env(const View& v, int64_t i, const Env& e) {
   unsigned f = (unsigned)(e.qvalid[0] & 0xff) | ((unsigned)(e.qvalid[1] & 0xff) << 8) |
                ((unsigned)(e.live & 0xff) << 16) | ((unsigned)(e.winner & 0xff) << 24);
-#ifdef SK_STATE_NT
-  // A/B build: streaming state stores (for batches far past the Infinity Cache)
-  typedef int v4i __attribute__((ext_vector_type(4)));
-  typedef double v2d __attribute__((ext_vector_type(2)));
-  typedef int v2i __attribute__((ext_vector_type(2)));
-  __builtin_nontemporal_store((v4i){e.px[0], e.py[0], e.px[1], e.py[1]}, (v4i*)(v.pos + i));
-  __builtin_nontemporal_store((v2d){e.rot[0], e.rot[1]}, (v2d*)(v.rot + i));
-  __builtin_nontemporal_store((v4i){e.qx[0], e.qy[0], e.qx[1], e.qy[1]}, (v4i*)(v.qpos + i));
-  __builtin_nontemporal_store((v2d){e.qrot[0], e.qrot[1]}, (v2d*)(v.qrot + i));
-  __builtin_nontemporal_store((v4i){e.qcd[0], e.qage[0], e.qcd[1], e.qage[1]}, (v4i*)(v.qcdage + i));
-  __builtin_nontemporal_store((v2i){e.ticks, (int)f}, (v2i*)(v.misc + i));
-#else
   v.pos[i] = make_int4(e.px[0], e.py[0], e.px[1], e.py[1]);
   v.rot[i] = make_double2(e.rot[0], e.rot[1]);
   v.qpos[i] = make_int4(e.qx[0], e.qy[0], e.qx[1], e.qy[1]);
   v.qrot[i] = make_double2(e.qrot[0], e.qrot[1]);
   v.qcdage[i] = make_int4(e.qcd[0], e.qage[0], e.qcd[1], e.qage[1]);
   v.misc[i] = make_int2(e.ticks, (int)f);
-#endif
 }
 
 // store_env for the fused steps: the projectile-rotation plane changes only
@@ -199,24 +180,12 @@ __device__ __forceinline__ void store_env_q(const View& v, int64_t i, const Env&
                ((unsigned)(e.live & 0xff) << 16) | ((unsigned)(e.winner & 0xff) << 24);
   const bool qrot_changed = (int)(__double_as_longlong(e.qrot[0]) != __double_as_longlong(q_old0)) |
                             (int)(__double_as_longlong(e.qrot[1]) != __double_as_longlong(q_old1));
-#ifdef SK_STATE_NT
-  typedef int v4i __attribute__((ext_vector_type(4)));
-  typedef double v2d __attribute__((ext_vector_type(2)));
-  typedef int v2i __attribute__((ext_vector_type(2)));
-  __builtin_nontemporal_store((v4i){e.px[0], e.py[0], e.px[1], e.py[1]}, (v4i*)(v.pos + i));
-  __builtin_nontemporal_store((v2d){e.rot[0], e.rot[1]}, (v2d*)(v.rot + i));
-  __builtin_nontemporal_store((v4i){e.qx[0], e.qy[0], e.qx[1], e.qy[1]}, (v4i*)(v.qpos + i));
-  if (qrot_changed) __builtin_nontemporal_store((v2d){e.qrot[0], e.qrot[1]}, (v2d*)(v.qrot + i));
-  __builtin_nontemporal_store((v4i){e.qcd[0], e.qage[0], e.qcd[1], e.qage[1]}, (v4i*)(v.qcdage + i));
-  __builtin_nontemporal_store((v2i){e.ticks, (int)f}, (v2i*)(v.misc + i));
-#else
   v.pos[i] = make_int4(e.px[0], e.py[0], e.px[1], e.py[1]);
   v.rot[i] = make_double2(e.rot[0], e.rot[1]);
   v.qpos[i] = make_int4(e.qx[0], e.qy[0], e.qx[1], e.qy[1]);
   if (qrot_changed) v.qrot[i] = make_double2(e.qrot[0], e.qrot[1]);
   v.qcdage[i] = make_int4(e.qcd[0], e.qage[0], e.qcd[1], e.qage[1]);
   v.misc[i] = make_int2(e.ticks, (int)f);
-#endif
 }
 
 // ---------------------------------------------------------------- lane pairs
@@ -626,11 +595,6 @@ __device__ __forceinline__ void tick_env_fast(const Cfg& c, Env& e, float a0_mov
 // for |rot| < 1.6e6).  A wave with any such lane, or with |rot| past that
 // range, or a NaN action, evaluates the fired projectiles' sincos exactly
 // (~1e-5 of waves).  Bit for bit tick_env_m's result.
-// SK_CARRY_BRANCHFREE = 0 (A/B builds): tick_env_carry's commits as the
-// per-method helpers' branches
-#ifndef SK_CARRY_BRANCHFREE
-#define SK_CARRY_BRANCHFREE 1
-#endif
 struct TrigCarry {
   double kr[2], kq[2];          // keys: m[p] = sincos(kr[p]), tq[p] = sincos(kq[p])
   sktrig::SinCos m[2], tq[2];
@@ -717,13 +681,13 @@ __device__ __forceinline__ void tick_env_carry(const Cfg& c, Env& e, TrigCarry& 
     if (f1) t1 = x1;
     fast0 = fast1 = false;
   }
-#if SK_CARRY_BRANCHFREE
   // The rest as selects, no branch: both players' chains (and both
   // projectiles') are independent, and with one wave per SIMD the tick is a
   // latency chain, so they must interleave; exec-mask branches around each
   // player's shoot / projectile / hit test had serialised them (per-phase
   // stamps, -DSK_TRACE_MULTI_WAIT: tools/trace_multi.py --wait).  Every value
-  // is the branchy form's expression; only the commits are selects.
+  // is the expression of the per-method helpers (move_direction_sc, shoot,
+  // projectile_tick_sc, collide_s); only the commits are selects.
   const sktrig::SinCos mm[2] = {t.m[0], t.m[1]};
   const float am[2] = {a0_move, a1_move};
   const double rn[2] = {rn0, rn1};
@@ -773,36 +737,6 @@ __device__ __forceinline__ void tick_env_carry(const Cfg& c, Env& e, TrigCarry& 
   const bool h2 = live && !h1 && hit_test_s(c, e.px[1], e.py[1], e.qx[0], e.qy[0], e.qvalid[0]);
   e.winner = h1 ? 1 : (h2 ? 2 : e.winner);
   e.live = (h1 || h2) ? 0 : e.live;
-#else
-  // do_actions(1, ...), do_actions(2, ...)  SkillshotLearner.py:206-213
-  move_direction_sc(c, e.px[0], e.py[0], t.m[0], (double)a0_move);
-  e.rot[0] = rn0;
-  shoot(c, e, 0);
-  move_direction_sc(c, e.px[1], e.py[1], t.m[1], (double)a1_move);
-  e.rot[1] = rn1;
-  shoot(c, e, 1);
-  // game_tick  SkillshotGame.py:115-122 (Projectile.py:38-53)
-  if (e.live) {
-    e.ticks += 1;
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-      if (e.qvalid[p]) {
-        const sktrig::SinCos tt = p ? t1 : t0;
-        const bool fast = p ? fast1 : fast0;
-        const float ex = p ? ex1 : ex0, ey = p ? ey1 : ey0;
-        const double sp = (double)c.qspeed;
-        const int nx = fast ? e.qx[p] - (int)rintf(ex) : (int)__builtin_rint((double)e.qx[p] - tt.s * sp);
-        const int ny = fast ? e.qy[p] - (int)rintf(ey) : (int)__builtin_rint((double)e.qy[p] - tt.c * sp);
-        bool ok = (nx + c.qsize <= c.W) & (nx >= 0) & (ny + c.qsize <= c.H) & (ny >= 0);
-        if (ok) { e.qx[p] = nx; e.qy[p] = ny; } else { e.qvalid[p] = 0; }
-      }
-      e.qcd[p] -= 1;
-      e.qage[p] += 1;
-    }
-    collide_s(c, e.px[0], e.py[0], e.qx[0], e.qy[0], e.qvalid[0], e.px[1], e.py[1], e.qx[1], e.qy[1],
-              e.qvalid[1], e.live, e.winner);
-  }
-#endif
 }
 
 // ---------------------------------------------------------------- features
@@ -912,23 +846,9 @@ __device__ __forceinline__ int future_flag_interval(const Cfg& c, int qx, int qy
 }
 
 // the same flag as a value (callers that store it themselves)
-#if defined(SK_ABL_INLINEREDO)  // timing ablation: the redo inlined (no call)
-__device__ __forceinline__ float future_flag_cr(const Cfg& c, int qx, int qy, double qrot, int ox, int oy) {
-  return future_collision_g(c, qx, qy, ox, oy, sktan::tan_cr(-qrot + kPi2)) ? 1.0f : 0.0f;
-}
-#elif defined(SK_ABL_TRIVCALL)  // timing ablation only: a trivial out-of-line redo (wrong on ambiguous lanes)
-__device__ __attribute__((noinline)) float future_flag_cr(const Cfg& c, int qx, int qy, double qrot, int ox, int oy) {
-  return future_collision_g(c, qx, qy, ox, oy, qrot * 3.0) ? 1.0f : 0.0f;
-}
-#elif defined(SK_ABL_CHEAPREDO)  // timing ablation only: the redo without tan_cr (wrong on ambiguous lanes)
-__device__ __forceinline__ float future_flag_cr(const Cfg& c, int qx, int qy, double qrot, int ox, int oy) {
-  return future_collision_g(c, qx, qy, ox, oy, qrot * 3.0) ? 1.0f : 0.0f;
-}
-#else
 __device__ __attribute__((noinline)) float future_flag_cr(const Cfg& c, int qx, int qy, double qrot, int ox, int oy) {
   return future_collision_g(c, qx, qy, ox, oy, sktan::tan_cr(-qrot + kPi2)) ? 1.0f : 0.0f;
 }
-#endif
 
 // the obs rows [2][N][12] of env i were stored from env state e; amb bit p
 // marks player p's flag for redoing
@@ -1045,9 +965,6 @@ __device__ __forceinline__ double grad_from_sincos(double qrot, sktrig::SinCos q
   const double bb = y - kPi2;
   const double err = (kPi2 - (y - bb)) + (-qrot - bb);
   const double eta = kPi2Lo + err;
-#ifdef SK_ABL_NODIV  // timing ablation only: wrong values, no fp64 division
-  return fma(-eta, qt.s, qt.c) * fma(eta, qt.c, qt.s);
-#endif
   return fma(-eta, qt.s, qt.c) / fma(eta, qt.c, qt.s);
 }
 
@@ -1068,17 +985,9 @@ __device__ __forceinline__ void obs12_sc(const Cfg& c, int px, int py, double ro
   out[8] = (float)((double)qy * c.inv_H);
   out[9] = (float)(((py_mod2_fast(qrot) * kPi) / 2.0) * kPi);
   out[10] = (float)(fabs(fma(qt.c, (double)ex, -(qt.s * (double)ey))) * c.inv_max_dist);
-#ifdef SK_ABL_NOFLAG  // timing ablation only: the flag without its gradient / margin test
-  out[11] = (float)(qvalid & (qx > ox));
-  *amb = false;
-#else
   const double g = grad_from_sincos(qrot, qt);
   if (gq) *gq = g;
   out[11] = future_collision_s(c, qx, qy, qvalid, ox, oy, g, amb) ? 1.0f : 0.0f;
-#ifdef SK_ABL_NOAMB  // timing ablation only: never take the correctly rounded redo
-  *amb = false;
-#endif
-#endif
 }
 
 // both players' obs of one env from the projectile sincos the tick used

@@ -1,18 +1,33 @@
 // sk_engine.hip — libskillshot: batched Skillshot env kernels for gfx950 and
 // the C ABI declared in include/skillshot.h.
 //
-// Kernels (one lane = one env; 256-lane workgroups; every SoA plane moved
-// with one 16-byte-per-lane load/store):
-//   k_step            fused learner tick: do_actions x2 + game_tick + obs/reward
-//                     + done/winner + masked auto-reset  (the hot path, K1+K2+K3)
-//   k_rollout_random  n ticks of the random policy in one launch, state held in
-//                     registers, in-kernel Philox actions (K4 fused)
-//   k_gen_actions     random-policy actions into HBM (K4)
-//   k_reset / k_move_* / k_shoot / k_game_tick / k_observe / k_features:
-//                     the reference's per-method API, batched
+// Step kernels (the SoA planes of include/skillshot.h moved 16 bytes per game,
+// or 8 per player, per load / store):
+//   one tick per launch (sk_env_step; SK_STEP_VARIANT)
+//     k_step              one lane per game, fp64 trig: do_actions x2 +
+//                         game_tick + obs / reward + done / winner + masked
+//                         auto-reset
+//     k_step_split        two lanes per game, one per player (small batches)
+//     k_step_fast         fp32 trig with an exact fp64 redo (large batches)
+//   n ticks per launch (sk_env_step_multi, sk_env_step_multi_obs;
+//   SK_MULTI_*): the state makes its round trip through memory every tick,
+//   the launch boundary is paid once
+//     k_step_multi        one lane per game, step-only; between ticks the
+//                         88-B exchange format or a packed 48-B form, the
+//                         action slab a tick ahead in registers or through a
+//                         feed wave and LDS
+//     k_step_split_multi  two lanes per game, step-only or with obs / reward;
+//                         optionally an action-slab prefetch wave
+//     both run the carried-sincos tick: tick_env_carry (sk_device.hpp) and
+//     split_tick_carry (below)
+//   k_rollout_random      n ticks of the random policy in one launch, state
+//                         held in registers, in-kernel Philox actions
+// Around them: k_gen_actions (random-policy actions into HBM), k_reset /
+// k_move_* / k_shoot / k_game_tick / k_observe / k_features (the reference's
+// per-method API, batched), and the host side of the C ABI, which chooses
+// among the kernels above (step_multi: geometry, workgroup, pack, prefetch).
 // Episode counters: wavefront ballots + popcount into one 128-B slot line per
-// wave, read-modify-written without atomics (see "counters" below).
-#include <hip/hip_ext.h>
+// wave, read-modify-written without atomics (sk_step.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -27,30 +42,6 @@
 #include "sk_step.hpp"
 
 using namespace sk;
-
-// k_step_multi's action slabs are loaded SK_ACT_AHEAD ticks before their
-// tick, into registers, after that earlier tick's state loads (0: with the
-// tick's own state loads).  The 400-slab ring is larger than the Infinity
-// Cache, so a slab comes from HBM, later than the state from the fabric; a
-// tick's loads are consumed in issue order (vmcnt), so its wait was the
-// slab's HBM latency (65,536 games, 20-tick launches: 2.55 us per tick with
-// the HBM ring against 2.04 with an 8-slab ring held in cache;
-// profiles/r06f_multi_pack_pf_ring_sweep.jsonl).  Issued one tick ahead, the
-// slab's loads are older than the state loads its tick waits for by a whole
-// tick; more ticks ahead gain nothing, since tick t + 1 waits (in issue order)
-// for every load tick t issued.
-#ifndef SK_ACT_AHEAD
-#define SK_ACT_AHEAD 1
-#endif
-#ifndef SK_EARLY_STORE
-#define SK_EARLY_STORE 1
-#endif
-
-// k_step_multi carries each tick's sincos to the next (tick_env_carry); 0:
-// every tick evaluates its four (A/B: tools/build_variant.sh -DSK_MULTI_CARRY=0)
-#ifndef SK_MULTI_CARRY
-#define SK_MULTI_CARRY 1
-#endif
 
 struct sk_env {
   int32_t n;
@@ -234,16 +225,10 @@ __global__ void __launch_bounds__(kStepBlock) k_step(StepArgs a, Cfg c) {
       }
     }
     d = (!e.live) || (e.ticks >= a.tick_limit);  // SkillshotLearner.py:302
-#ifdef SK_DONE_NT
-    if (a.done) __builtin_nontemporal_store((uint8_t)d, a.done + i);
-    if (a.winner) __builtin_nontemporal_store((uint8_t)e.winner, a.winner + i);
-#else
     if (a.done) a.done[i] = (uint8_t)d;
     if (a.winner) a.winner[i] = (uint8_t)e.winner;
-#endif
   }
   const int fin_winner = in ? e.winner : 0, fin_ticks = in ? e.ticks : 0;  // before the restart
-  (void)fin_winner; (void)fin_ticks; (void)wc;  // unused in the -DSK_ABL_NOCTR timing build
   if (in && d && a.auto_reset) {
     if (a.random_positions) {
       if (a.n >= kEarlyDrawMinEnvs) reset_random_u(c, e, ru);
@@ -263,9 +248,7 @@ __global__ void __launch_bounds__(kStepBlock) k_step(StepArgs a, Cfg c) {
     if (amb) fix_future_flags_g(c, e, amb, g0, g1, a.obs_reset, a.n, i);  // (restarted: amb = 0)
   }
   if (in) store_env_q(a.v, i, e, q_old0, q_old1);
-#ifndef SK_ABL_NOCTR  // timing ablation only
   if (a.ctr) wave_count(a.ctr, wc, d, fin_winner, fin_ticks);
-#endif
   if (!in) return;
 #ifdef SK_TRACE_STEP
   __builtin_amdgcn_s_waitcnt(0);
@@ -338,13 +321,8 @@ __global__ void __launch_bounds__(kStepBlock) k_step_fast(StepArgs a, Cfg c) {
       }
     }
     d = (!e.live) || (e.ticks >= a.tick_limit);  // SkillshotLearner.py:302
-#ifdef SK_DONE_NT
-    if (a.done) __builtin_nontemporal_store((uint8_t)d, a.done + i);
-    if (a.winner) __builtin_nontemporal_store((uint8_t)e.winner, a.winner + i);
-#else
     if (a.done) a.done[i] = (uint8_t)d;
     if (a.winner) a.winner[i] = (uint8_t)e.winner;
-#endif
   }
   if (!in) return;
   const int fin_winner = e.winner, fin_ticks = e.ticks;  // before the restart
@@ -515,25 +493,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t raw_rsrc(const void* base) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, -1, 0x00020000);
 }
 
-template <int POL>
-__device__ __forceinline__ void load_env_port(const MultiArgs& a, __amdgpu_buffer_rsrc_t r, int64_t i, Env& e) {
-  if constexpr (POL == 0) {
-    load_env(a.v, i, e);
-  } else {
-    const uint32_t o16 = (uint32_t)i * 16u, o8 = (uint32_t)i * 8u;
-    const skb4i p = __builtin_amdgcn_raw_buffer_load_b128(r, o16 + a.off[0], 0, 16);
-    const skb4i rb = __builtin_amdgcn_raw_buffer_load_b128(r, o16 + a.off[1], 0, 16);
-    const skb4i q = __builtin_amdgcn_raw_buffer_load_b128(r, o16 + a.off[2], 0, 16);
-    const skb4i qb = __builtin_amdgcn_raw_buffer_load_b128(r, o16 + a.off[3], 0, 16);
-    const skb4i ca = __builtin_amdgcn_raw_buffer_load_b128(r, o16 + a.off[4], 0, 16);
-    const skb2i m = __builtin_amdgcn_raw_buffer_load_b64(r, o8 + a.off[5], 0, 16);
-    const skb2d rr = __builtin_bit_cast(skb2d, rb), qr = __builtin_bit_cast(skb2d, qb);
-    decode_env(EnvRaw{make_int4(p.x, p.y, p.z, p.w), make_double2(rr.x, rr.y), make_int4(q.x, q.y, q.z, q.w),
-                      make_double2(qr.x, qr.y), make_int4(ca.x, ca.y, ca.z, ca.w), make_int2(m.x, m.y)},
-               e);
-  }
-}
-
 // store_env_q through the port: the projectile-rotation plane only where it
 // changed (a projectile fired, or the game restarted) unless force_q (the
 // previous tick's state was packed: this plane is stale)
@@ -585,33 +544,6 @@ __device__ __forceinline__ int pack_cah(int cd, int age, unsigned hi) {
 }
 
 template <int POL>
-__device__ __forceinline__ void load_env_pack(const MultiArgs& a, __amdgpu_buffer_rsrc_t rp, int64_t i, Env& e) {
-  skb4i rb, qb, sb;
-  if constexpr (POL == 0) {
-    const skb4i* P = reinterpret_cast<const skb4i*>(a.pack);
-    rb = P[i];
-    qb = P[a.n + i];
-    sb = P[2 * a.n + i];
-  } else {
-    const uint32_t o = (uint32_t)i * 16u, plane = (uint32_t)a.n * 16u;
-    rb = __builtin_amdgcn_raw_buffer_load_b128(rp, o, 0, 16);
-    qb = __builtin_amdgcn_raw_buffer_load_b128(rp, o + plane, 0, 16);
-    sb = __builtin_amdgcn_raw_buffer_load_b128(rp, o + 2u * plane, 0, 16);
-  }
-  const skb2d rr = __builtin_bit_cast(skb2d, rb), qr = __builtin_bit_cast(skb2d, qb);
-  e.rot[0] = rr.x; e.rot[1] = rr.y;
-  e.qrot[0] = qr.x; e.qrot[1] = qr.y;
-  const unsigned s0 = (unsigned)sb.x, c0 = (unsigned)sb.y, s1 = (unsigned)sb.z, c1 = (unsigned)sb.w;
-  e.px[0] = s0 & 0xff; e.py[0] = (s0 >> 8) & 0xff; e.qx[0] = (s0 >> 16) & 0xff; e.qy[0] = s0 >> 24;
-  e.px[1] = s1 & 0xff; e.py[1] = (s1 >> 8) & 0xff; e.qx[1] = (s1 >> 16) & 0xff; e.qy[1] = s1 >> 24;
-  e.qcd[0] = (int)(signed char)(c0 & 0xff); e.qage[0] = (c0 >> 8) & 0xff;
-  e.qcd[1] = (int)(signed char)(c1 & 0xff); e.qage[1] = (c1 >> 8) & 0xff;
-  e.ticks = (int)(c0 >> 16);
-  const unsigned fl = c1 >> 16;
-  e.qvalid[0] = fl & 1; e.qvalid[1] = (fl >> 1) & 1; e.live = (fl >> 2) & 1; e.winner = (fl >> 3) & 3;
-}
-
-template <int POL>
 __device__ __forceinline__ void store_env_pack(const MultiArgs& a, __amdgpu_buffer_rsrc_t rp, int64_t i, const Env& e,
                                                bool store_q) {
   const skb4i rb = __builtin_bit_cast(skb4i, (skb2d){e.rot[0], e.rot[1]});
@@ -638,10 +570,11 @@ struct MultiLane {
   unsigned n_done, n_h1, n_h2, t_sum;  // this lane's episode counts (t_sum < n_ticks * tick_limit)
 };
 
-// one tick of k_step_multi on slab `slab` of the action ring.  State first,
-// actions last (k_step's order: the players' sincos of the old rotations
-// run while the slab arrives).  Prefetching the slab a tick ahead was slower
-// (65,536 games 2.51 vs 2.36 us per tick, 8,192 split 1.71 vs 1.59;
+// one tick of k_step_multi.  The tick's own loads are its state; its action
+// slab is already in registers (loaded a tick ahead) or in LDS (the feed
+// wave), see k_step_multi.  Round 3's first prefetch of the next tick's slab
+// (before the tick was split at its loads) was slower (65,536 games 2.51 vs
+// 2.36 us per tick, 8,192 split 1.71 vs 1.59;
 // profiles/r03d_multi_prefetch_sweep.jsonl): vector memory returns in issue
 // order, so the next tick's state waited for the prefetched HBM loads anyway.
 // `packed` (wave-uniform): where the state lives now; `last`: the final tick
@@ -665,7 +598,12 @@ struct MultiRaw {  // one tick's loads as issued, decoded at the tick's start
   float2 act[2];    // both players' actions
 };
 
-template <int POL, bool PACK, bool ACT = true>
+// the state loads of one tick (w.act is filled by k_step_multi: the slab
+// loaded a tick ahead, or the feed wave's LDS slot).  `slab` is no longer
+// read here; without the parameter the compiler orders k_step_multi's
+// register copies at the loop's back edge differently, so it goes with the
+// next change that is meant to alter the kernel.
+template <int POL, bool PACK>
 __device__ __forceinline__ void multi_load(const MultiArgs& a, __amdgpu_buffer_rsrc_t r, __amdgpu_buffer_rsrc_t rp,
                                            const MultiLane& L, int64_t slab, bool packed, MultiRaw& w) {
   const uint32_t o16 = (uint32_t)L.ic * 16u, o8 = (uint32_t)L.ic * 8u;
@@ -694,11 +632,6 @@ __device__ __forceinline__ void multi_load(const MultiArgs& a, __amdgpu_buffer_r
     w.m = __builtin_amdgcn_raw_buffer_load_b64(r, o8 + a.off[5], 0, 16);
   }
   __builtin_amdgcn_sched_barrier(0);
-  if constexpr (ACT) {
-    w.act[0] = load_action(a.actions + slab * 2 * a.n + L.ic);
-    w.act[1] = load_action(a.actions + slab * 2 * a.n + a.n + L.ic);
-    __builtin_amdgcn_sched_barrier(0);
-  }
 }
 
 template <bool PACK>
@@ -792,17 +725,9 @@ __device__ __forceinline__ void multi_compute(const MultiArgs& a, const Cfg& c, 
   // 2.50 vs 2.51 and 3.37 vs 2.71 us per tick; profiles/
   // r03i_multi_fast_early_sweep.jsonl).  Round 6: the same values with
   // the sincos carried from the previous tick (tick_env_carry, sk_device.hpp)
-#if SK_MULTI_CARRY
   tick_env_carry(c, e, tc, L.in, acts[0].x, acts[0].y, acts[1].x, acts[1].y);
-#else
-  (void)tc;
-  bool k0, k1;
-  const sktrig::SinCos m0 = sktrig::sincos_bf(e.rot[0], &k0);
-  const sktrig::SinCos m1 = sktrig::sincos_bf(e.rot[1], &k1);
-  tick_env_m(c, e, m0, m1, k0 & k1, (double)acts[0].x, (double)acts[0].y, (double)acts[1].x, (double)acts[1].y);
-#endif
   SK_MTW(tick, 2);
-  // SK_EARLY_STORE (88-B form): the state goes out right after the tick,
+  // The 88-B form stores early: the state goes out right after the tick,
   // before the done outputs and the restart; a lane that restarts stores its
   // planes again (its later stores win: same wave, same addresses, issue
   // order).  The stores then drain while the wave finishes the tick instead
@@ -810,7 +735,7 @@ __device__ __forceinline__ void multi_compute(const MultiArgs& a, const Cfg& c, 
   // us per tick at 400 ticks per launch, 2.6 -> 2.5 at 20; profiles/r06n_*).
   // Storing pos / rot / qrot earlier still, between do_actions and game_tick,
   // was slower (2.02 -> 2.13, 2.54 -> 2.59; profiles/r06o_*).
-  constexpr bool EARLY = SK_EARLY_STORE && !PACK;
+  constexpr bool EARLY = !PACK;
   if constexpr (EARLY) {
     if (L.in) store_env_port<POL>(a, r, L.i, e, q_old0, q_old1, packed);
   }
@@ -835,9 +760,7 @@ __device__ __forceinline__ void multi_compute(const MultiArgs& a, const Cfg& c, 
       reset_fixed(c, e);
     }
   }
-#if SK_MULTI_CARRY
   if (!last) carry_note(tc, e);
-#endif
   SK_MTW(tick, 3);
   bool to_pack = false;
   if constexpr (PACK) {
@@ -1002,11 +925,21 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_multi(MultiArg
   int t = 0;
   TrigCarry tc;
   tc.have = tc.pend = false;
-  // the action pipeline (SK_ACT_AHEAD): tick t reads the slab from one
+  // The action pipeline (no feed wave): a tick's action slab is loaded one
+  // tick before it, into registers, after that earlier tick's state loads.
+  // The 400-slab ring is larger than the Infinity Cache, so a slab comes from
+  // HBM, later than the state from the fabric; a tick's loads are consumed in
+  // issue order (vmcnt), so with the slab among them its wait was the slab's
+  // HBM latency (65,536 games, 20-tick launches: 2.55 us per tick with the
+  // HBM ring against 2.04 with an 8-slab ring held in cache;
+  // profiles/r06f_multi_pack_pf_ring_sweep.jsonl).  Issued one tick ahead, the
+  // slab's loads are older than the state loads its tick waits for by a whole
+  // tick; more ticks ahead gain nothing, since tick t + 1 waits (in issue
+  // order) for every load tick t issued.  Tick t reads the slab from one
   // register pair while the next tick's slab loads into the other; the loop
   // runs two ticks per iteration so the pairs alternate without a copy (a
   // copy of the pair just loaded waits for that load)
-  constexpr bool AHEAD = PF == 0 && SK_ACT_AHEAD != 0;
+  constexpr bool AHEAD = PF == 0;
   float2 pa0[2], pa1[2];
   if constexpr (AHEAD) {
     pa0[0] = load_action(a.actions + slab * 2 * a.n + L.ic);
@@ -1017,7 +950,7 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_multi(MultiArg
   auto one_tick = [&](float2 (&cur)[2], float2 (&nxt)[2]) {
     MultiRaw w;
     if constexpr (PF > 0) asm volatile("s_barrier" ::: "memory");  // barrier t (feed_wave)
-    multi_load<POL, PACK, !AHEAD && PF == 0>(a, r, rp, L, slab, packed, w);
+    multi_load<POL, PACK>(a, r, rp, L, slab, packed, w);  // the state; the slab comes from LDS or from `cur`
     if constexpr (PF > 0) {  // the slab from LDS (feed_wave)
       const int gl = threadIdx.x & 63;
       w.act[0] = feed[take].act[0][gl];
@@ -1036,10 +969,8 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_multi(MultiArg
       w.act[1] = cur[1];
       __builtin_amdgcn_sched_barrier(0);
     }
-#if SK_MULTI_CARRY
     if (tc.pend) carry_advance(tc);  // the last tick's rotations, while this tick's loads fly
     __builtin_amdgcn_sched_barrier(0);
-#endif
 #ifdef SK_TRACE_MULTI_WAIT
     if (t < 5) {
       SK_MTW(t, 0);
@@ -1084,22 +1015,6 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_multi(MultiArg
 // their tick: 8,192 games 1.98 vs 1.59 us; profiles/r03f_multi_pack*_sweep.jsonl
 // vs r03c_multi_split_sweep.jsonl).
 template <int POL>
-__device__ __forceinline__ double ld_half_d(const MultiArgs& a, __amdgpu_buffer_rsrc_t r, int k, const double* plane,
-                                            int64_t h) {
-  if constexpr (POL == 0) return plane[h];
-  else return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, (uint32_t)h * 8u + a.off[k], 0, 16));
-}
-template <int POL>
-__device__ __forceinline__ int2 ld_half_i(const MultiArgs& a, __amdgpu_buffer_rsrc_t r, int k, const int2* plane,
-                                          int64_t h) {
-  if constexpr (POL == 0) {
-    return plane[h];
-  } else {
-    const skb2i v = __builtin_amdgcn_raw_buffer_load_b64(r, (uint32_t)h * 8u + a.off[k], 0, 16);
-    return make_int2(v.x, v.y);
-  }
-}
-template <int POL>
 __device__ __forceinline__ void st_half_d(const MultiArgs& a, __amdgpu_buffer_rsrc_t r, int k, double* plane, int64_t h,
                                           double v) {
   if constexpr (POL == 0) plane[h] = v;
@@ -1118,167 +1033,17 @@ struct SplitLane {
   unsigned n_done, n_h1, n_h2, t_sum;  // this pair's episode counts (lane p = 0 counts)
 };
 
-// OBS (sk_env_step_multi_obs, the full contract of configs 3-5): the tick
-// also writes the post-tick observation and reward of its player
-// (k_step_split's obs12_sc epilogue from the tick's sin/cos, the looking or
-// simple reward) into output slab `so`, and settles an ambiguous
-// future-collision flag after its state stores, as k_step_split does.
-template <int POL, bool OBS>
-__device__ __forceinline__ void split_multi_tick(const MultiArgs& a, const Cfg& c, __amdgpu_buffer_rsrc_t r,
-                                                 SplitLane& L, WaveCtr& wc, int64_t so, uint64_t step, int64_t slab) {
-  int2* const pos2 = reinterpret_cast<int2*>(a.v.pos);
-  double* const rot1 = reinterpret_cast<double*>(a.v.rot);
-  int2* const qpos2 = reinterpret_cast<int2*>(a.v.qpos);
-  double* const qrot1 = reinterpret_cast<double*>(a.v.qrot);
-  int2* const ca2 = reinterpret_cast<int2*>(a.v.qcdage);
-  const int p = L.p;
-  double rot, qrot;
-  int px, py, qx, qy, qcd, qage, ticks, qvalid, live, winner;
-  {
-    // k_step_split's load order: rotation first
-    rot = ld_half_d<POL>(a, r, 1, rot1, L.hc);
-    qrot = ld_half_d<POL>(a, r, 3, qrot1, L.hc);
-    const int2 pp = ld_half_i<POL>(a, r, 0, pos2, L.hc);
-    const int2 ca = ld_half_i<POL>(a, r, 4, ca2, L.hc);
-    const int2 qq = ld_half_i<POL>(a, r, 2, qpos2, L.hc);
-    const int2 mi = ld_half_i<POL>(a, r, 5, a.v.misc, L.ic);
-    px = pp.x; py = pp.y; qx = qq.x; qy = qq.y; qcd = ca.x; qage = ca.y; ticks = mi.x;
-    const int flags = mi.y;
-    qvalid = ((unsigned)flags >> (8 * p)) & 0xff;
-    live = ((unsigned)flags >> 16) & 0xff;
-    winner = ((unsigned)flags >> 24) & 0xff;
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  const float2 act = load_action(a.actions + slab * 2 * a.n + (int64_t)p * a.n + L.ic);  // action last
-  __builtin_amdgcn_sched_barrier(0);
-  bool k0, k1, k2 = true;
-#ifdef SK_ABL_NOSC  // timing ablation only (tools/ab_split4.sh): no sincos at all
-  sktrig::SinCos m{rot * 1e-9, 1.0};
-  k0 = true;
-#else
-  sktrig::SinCos m = sktrig::sincos_bf(rot, &k0);
-#endif
-  const double q_old = qrot;
-  // do_actions(p+1, ...)  SkillshotLearner.py:206-213 (both sincos up front)
-  const double rn = rot + clamp_action((double)act.y) * c.look;
-  const double qn = (qcd <= 0) ? rn : qrot;
-#if defined(SK_ABL_NOQSC) || defined(SK_ABL_NOSC)  // timing ablation only: no projectile sincos
-  sktrig::SinCos tq{qn * 1e-9, 1.0};
-  k1 = true;
-#else
-  sktrig::SinCos tq = sktrig::sincos_bf(qn, &k1);
-#endif
-  // the post-look rotation's sin/cos for the obs epilogue (fp32: obs12_sc)
-  sktrig::SinCosF pr{0.0f, 1.0f};
-  if constexpr (OBS) pr = sktrig::sincos_fast(rn, &k2);
-  if (!(k0 & k1 & k2)) {
-    if (!k0) m = sincos_lib(rot);
-    if (!k1) tq = sincos_lib(qn);
-    if (!k2) {
-      const sktrig::SinCos rr = sincos_lib(rn);
-      pr.s = (float)rr.s;
-      pr.c = (float)rr.c;
-    }
-  }
-  move_direction_sc(c, px, py, m, (double)act.x);
-  rot = rn;
-  shoot_s(c, px, py, rot, qx, qy, qrot, qcd, qage, qvalid);
-  // game_tick  SkillshotGame.py:115-122 (live is identical in both lanes)
-  if (live) {
-    ticks += 1;
-    projectile_tick_sc(c, qx, qy, tq, qcd, qage, qvalid);
-  }
-  const int opx = pair_swap(px), opy = pair_swap(py);
-  const int oqx = pair_swap(qx), oqy = pair_swap(qy), oqv = pair_swap(qvalid);
-  if (live) {
-    if (p == 0) collide_s(c, px, py, qx, qy, qvalid, opx, opy, oqx, oqy, oqv, live, winner);
-    else collide_s(c, opx, opy, oqx, oqy, oqv, px, py, qx, qy, qvalid, live, winner);
-  }
-  ctr_settle(wc);  // every load of this tick consumed (see multi_tick)
-  const bool d = L.in && ((!live) || (ticks >= a.tick_limit));  // SkillshotLearner.py:302
-  bool amb = false;
-  double gq = 0.0;  // the fast projectile gradient (the ambiguous flag's interval check)
-  const int aqx = qx, aqy = qy;  // the post-tick projectile, for the flag's redo
-  const double aqrot = qrot;
-  if constexpr (OBS) {
-    if (L.in) {  // prepare_states / calculate_rewards_* (SkillshotLearner.py:512-603) of the post-tick state
-      float o[12], pd;
-      obs12_sc(c, px, py, rot, pr, qx, qy, qrot, tq, qcd, qvalid, opx, opy, o, &pd, &amb, &gq);
-      if (a.obs) store_obs(a.obs + so * 24 * a.n, a.n, p, L.i, o);
-      if (a.reward) {
-        float rw;
-        if (a.reward_kind == SK_REWARD_SIMPLE) {  // a difference of distances: fp64 roots
-          const double mine = dist_point_point(qx, qy, opx, opy);
-          const double theirs = dist_point_point(oqx, oqy, px, py);
-          rw = (float)(mine - theirs);
-        } else {
-          rw = (float)(-(double)pd / (double)c.W);
-        }
-        a.reward[so * 2 * a.n + (int64_t)p * a.n + L.i] = rw;
-      }
-    }
-  }
-  if (L.in && p == 0) {
-    if (a.done) a.done[so * a.out_stride + L.i] = (uint8_t)d;
-    if (a.winner) a.winner[so * a.out_stride + L.i] = (uint8_t)winner;
-  }
-  const bool dc = d && p == 0;
-  L.n_done += dc;
-  L.n_h1 += dc && winner == 1;
-  L.n_h2 += dc && winner == 2;
-  L.t_sum += dc ? (unsigned)ticks : 0u;
-  if (d && a.auto_reset) {  // SkillshotGame.__init__ :10-25 for this lane's player
-    if (a.random_positions) {
-      const U4 u = draw4(a.seed, (uint64_t)(a.env_offset + L.i), step, 1u);
-      px = u32_to_pos(p ? u.z : u.x, c.rlo, c.rhi);
-      py = u32_to_pos(p ? u.w : u.y, c.rlo, c.rhi);
-    } else {
-      px = p ? c.f2x : c.f1x;
-      py = p ? c.f2y : c.f1y;
-    }
-    rot = 0.0; qx = 0; qy = 0; qrot = 0.0; qcd = 0; qage = 0; qvalid = 0;
-    ticks = 0; live = 1; winner = 0;
-  }
-  const int ov = pair_swap(qvalid);
-  const bool qch = __double_as_longlong(qrot) != __double_as_longlong(q_old);
-  if (L.in) {
-    {
-      st_half_i<POL>(a, r, 0, pos2, L.h, px, py);
-      st_half_d<POL>(a, r, 1, rot1, L.h, rot);
-      st_half_i<POL>(a, r, 2, qpos2, L.h, qx, qy);
-      if (qch) st_half_d<POL>(a, r, 3, qrot1, L.h, qrot);
-      st_half_i<POL>(a, r, 4, ca2, L.h, qcd, qage);
-      if (p == 0) {
-        const unsigned f = (unsigned)(qvalid & 0xff) | ((unsigned)(ov & 0xff) << 8) |
-                           ((unsigned)(live & 0xff) << 16) | ((unsigned)(winner & 0xff) << 24);
-        st_half_i<POL>(a, r, 5, a.v.misc, L.i, ticks, (int)f);
-      }
-    }
-  }
-  if constexpr (OBS) {
-    // the future-collision flag within its margin of an edge, settled after
-    // this tick's state stores (k_step_split's tail rule): by the interval
-    // check unless it depends on g's last bits (then the correctly rounded tan)
-    if (amb && a.obs) {
-      const int fi = future_flag_interval(c, aqx, aqy, opx, opy, gq);
-      const float f = fi >= 0 ? (float)fi : future_flag_cr(c, aqx, aqy, aqrot, opx, opy);
-      a.obs[so * 24 * a.n + ((int64_t)p * a.n + L.i) * 12 + 11] = f;
-    }
-  }
-}
-
-// ---- the step-only split tick of round 6 (SK_SPLIT_CARRY): k_step_multi's
-// round-6 tick in the split geometry.  The lane's player's rotation sincos is
+// ---- the split tick (split_tick_carry): k_step_multi's carried-sincos tick
+// in the split geometry.  The lane's player's rotation sincos is
 // carried from the previous tick (evaluated at the top of the tick under its
 // loads, keyed by the rotation's bits), a projectile in flight keeps its
 // carried sincos, a fired one gets its step by fp32 angle addition with the
 // wave's exact fallback (tick_env_carry, sk_device.hpp); the commits are
 // selects; the action slab is loaded one tick ahead; the state halves are
 // stored right after the tick, before done / restart (a restarted game's
-// lanes store theirs again).  Bit for bit split_multi_tick<POL, false>.
-#ifndef SK_SPLIT_CARRY
-#define SK_SPLIT_CARRY 1
-#endif
+// lanes store theirs again).  Bit for bit k_step_split launched once per tick
+// (tests/test_multi_gpu.py and tests/test_multi_obs_gpu.py compare a launch
+// with one sk_env_step launch per tick).
 struct SplitCarry {
   double kr, kq;  // keys: m = sincos(kr), tq = sincos(kq)
   sktrig::SinCos m, tq;
@@ -1437,7 +1202,7 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
     live = (h1 || h2) ? 0 : live;
   }
   ctr_settle(wc);  // every load of this tick consumed (see multi_tick)
-  {  // the state out before done / restart (SK_EARLY_STORE's reason, k_step_multi)
+  {  // the state out before done / restart (multi_compute's early store, for its reason)
     const unsigned fl = (unsigned)(qvalid & 0xff) | ((unsigned)(oqv & 0xff) << 8) | ((unsigned)(live & 0xff) << 16) |
                         ((unsigned)(winner & 0xff) << 24);
     const bool qch = __double_as_longlong(qrot) != __double_as_longlong(q_old);
@@ -1547,42 +1312,33 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
   step_advance(a.step, step0, (uint64_t)a.n_ticks);
   const __amdgpu_buffer_rsrc_t r = raw_rsrc(a.base);
   int64_t slab = a.slab0, so = a.out0;
-  if constexpr (SK_SPLIT_CARRY) {
-    // the round-6 tick (split_tick_carry): the slab one tick ahead in the
-    // register pair this tick does not read, two ticks per iteration
-    const int64_t aoff = (int64_t)L.p * a.n + L.ic;
-    float2 pa0 = load_action(a.actions + slab * 2 * a.n + aoff), pa1;
-    int64_t pslab = slab + 1 == a.ring ? 0 : slab + 1;
-    SplitCarry tc;
-    tc.have = tc.pend = false;
-    int t = 0;
-    auto one_tick = [&](const float2& cur, float2& nxt) {
-      SplitRaw w;
-      if constexpr (PF > 0) __builtin_amdgcn_s_barrier();  // the prefetch wave (full contract at 512 lanes)
-      split_load_raw<POL>(a, r, L, w);
-      const int64_t ls = t + 1 < a.n_ticks ? pslab : slab;  // unconditional (see k_step_multi)
-      nxt = load_action(a.actions + ls * 2 * a.n + aoff);
-      __builtin_amdgcn_sched_barrier(0);
-      if (tc.pend) split_carry_advance(tc);  // the last tick's rotation, while this tick's loads fly
-      __builtin_amdgcn_sched_barrier(0);
-      split_tick_carry<POL, OBS>(a, c, r, L, wc, so, step0 + (uint64_t)t, w, cur, tc, t + 1 == a.n_ticks);
-      slab = slab + 1 == a.ring ? 0 : slab + 1;
-      pslab = pslab + 1 == a.ring ? 0 : pslab + 1;
-      so = so + 1 == a.out_slabs ? 0 : so + 1;
-    };
-    do {  // n_ticks >= 1 (host-checked)
-      one_tick(pa0, pa1);
-      if (++t >= a.n_ticks) break;
-      one_tick(pa1, pa0);
-    } while (++t < a.n_ticks);
-  } else {
-    for (int t = 0; t < a.n_ticks; ++t) {
-      if constexpr (PF > 0) __builtin_amdgcn_s_barrier();
-      split_multi_tick<POL, OBS>(a, c, r, L, wc, so, step0 + (uint64_t)t, slab);
-      slab = slab + 1 == a.ring ? 0 : slab + 1;
-      so = so + 1 == a.out_slabs ? 0 : so + 1;
-    }
-  }
+  // the slab one tick ahead in the register pair this tick does not read,
+  // two ticks per iteration (k_step_multi's action pipeline)
+  const int64_t aoff = (int64_t)L.p * a.n + L.ic;
+  float2 pa0 = load_action(a.actions + slab * 2 * a.n + aoff), pa1;
+  int64_t pslab = slab + 1 == a.ring ? 0 : slab + 1;
+  SplitCarry tc;
+  tc.have = tc.pend = false;
+  int t = 0;
+  auto one_tick = [&](const float2& cur, float2& nxt) {
+    SplitRaw w;
+    if constexpr (PF > 0) __builtin_amdgcn_s_barrier();  // the prefetch wave (full contract at 512 lanes)
+    split_load_raw<POL>(a, r, L, w);
+    const int64_t ls = t + 1 < a.n_ticks ? pslab : slab;  // unconditional (see k_step_multi)
+    nxt = load_action(a.actions + ls * 2 * a.n + aoff);
+    __builtin_amdgcn_sched_barrier(0);
+    if (tc.pend) split_carry_advance(tc);  // the last tick's rotation, while this tick's loads fly
+    __builtin_amdgcn_sched_barrier(0);
+    split_tick_carry<POL, OBS>(a, c, r, L, wc, so, step0 + (uint64_t)t, w, cur, tc, t + 1 == a.n_ticks);
+    slab = slab + 1 == a.ring ? 0 : slab + 1;
+    pslab = pslab + 1 == a.ring ? 0 : pslab + 1;
+    so = so + 1 == a.out_slabs ? 0 : so + 1;
+  };
+  do {  // n_ticks >= 1 (host-checked)
+    one_tick(pa0, pa1);
+    if (++t >= a.n_ticks) break;
+    one_tick(pa1, pa0);
+  } while (++t < a.n_ticks);
   if (a.ctr) {
     const unsigned c4[4] = {L.n_done, L.n_h1, L.n_h2, L.t_sum};
     uint64_t v[4];
@@ -1733,19 +1489,10 @@ __global__ void __launch_bounds__(kBlock) k_features(View v, int64_t n, double* 
   }
 }
 
-// A launch that records `e0` as its first wave starts and `e1` after its
-// last wave ends (hipExtLaunchKernel; either may be NULL): the kernel's own
-// duration on its stream, without the host-side gap between a separate
-// event record and the launch.
 template <typename... P, typename... A>
-static hipError_t launch_timed(void (*k)(P...), dim3 grid, dim3 block, hipStream_t s, hipEvent_t e0, hipEvent_t e1,
-                               A... args) {
-  if (!e0 && !e1) {
-    k<<<grid, block, 0, s>>>(args...);
-    return hipGetLastError();
-  }
-  void* argv[] = {static_cast<void*>(&args)...};
-  return hipExtLaunchKernel(reinterpret_cast<const void*>(k), grid, block, argv, 0, s, e0, e1, 0);
+static hipError_t launch(void (*k)(P...), dim3 grid, dim3 block, hipStream_t s, A... args) {
+  k<<<grid, block, 0, s>>>(args...);
+  return hipGetLastError();
 }
 
 // k_step_split_multi<POL, BLK, OBS> with its action-slab prefetch wave pf
@@ -1753,11 +1500,24 @@ static hipError_t launch_timed(void (*k)(P...), dim3 grid, dim3 block, hipStream
 template <int POL, int BLK, bool OBS>
 static hipError_t launch_split_multi(int pf, dim3 g, hipStream_t hs, const MultiArgs& a, const Cfg& c, int stagger) {
   if constexpr (POL == 1) {
-    if (pf == 1) return launch_timed(k_step_split_multi<1, BLK, OBS, 1>, g, dim3(BLK + 64), hs, nullptr, nullptr, a, c, stagger);
-    if (pf == 2) return launch_timed(k_step_split_multi<1, BLK, OBS, 2>, g, dim3(BLK + 64), hs, nullptr, nullptr, a, c, stagger);
-    if (pf > 2) return launch_timed(k_step_split_multi<1, BLK, OBS, 4>, g, dim3(BLK + 64), hs, nullptr, nullptr, a, c, stagger);
+    if (pf == 1) return launch(k_step_split_multi<1, BLK, OBS, 1>, g, dim3(BLK + 64), hs, a, c, stagger);
+    if (pf == 2) return launch(k_step_split_multi<1, BLK, OBS, 2>, g, dim3(BLK + 64), hs, a, c, stagger);
+    if (pf > 2) return launch(k_step_split_multi<1, BLK, OBS, 4>, g, dim3(BLK + 64), hs, a, c, stagger);
   }
-  return launch_timed(k_step_split_multi<POL, BLK, OBS>, g, dim3(BLK), hs, nullptr, nullptr, a, c, stagger);
+  return launch(k_step_split_multi<POL, BLK, OBS>, g, dim3(BLK), hs, a, c, stagger);
+}
+
+// k_step_multi<POL, PACK, BLK> with its feed wave pf ticks ahead (1, 2 or 4;
+// 0 none; only the write-through port's 88-B form on 64-lane workgroups has one)
+template <int POL, bool PACK, int BLK>
+static hipError_t launch_multi(int pf, hipStream_t hs, const MultiArgs& a, const Cfg& c, int early) {
+  const dim3 g((unsigned)((a.n + BLK - 1) / BLK));
+  if constexpr (POL == 1 && !PACK && BLK == kStepBlock) {
+    if (pf == 1) return launch(k_step_multi<1, false, BLK, 1>, g, dim3(BLK + 64), hs, a, c, early);
+    if (pf == 2) return launch(k_step_multi<1, false, BLK, 2>, g, dim3(BLK + 64), hs, a, c, early);
+    if (pf > 2) return launch(k_step_multi<1, false, BLK, 4>, g, dim3(BLK + 64), hs, a, c, early);
+  }
+  return launch(k_step_multi<POL, PACK, BLK>, g, dim3(BLK), hs, a, c, early);
 }
 
 // ------------------------------------------------------------------ host ABI
@@ -2497,7 +2257,6 @@ static int step_multi(sk_env* e, const float* actions, int64_t ring_slabs, int64
   // computes that player's observation, as k_step_split does)
   const bool split = full || (e->multi_split >= 0 ? e->multi_split != 0 : (int64_t)e->n <= kSplitMultiMaxEnvs);
   const hipStream_t hs = (hipStream_t)stream;
-  hipEvent_t e0 = nullptr, e1 = nullptr;  // launch_timed's events (A/B hook; unused by the ABI)
   hipError_t err;
   // the packed resident form in the lane-per-game kernel only (see
   // k_step_split_multi)
@@ -2554,40 +2313,25 @@ static int step_multi(sk_env* e, const float* actions, int64_t ring_slabs, int64
     // round-6 tick (early stores, the slab a tick ahead) 256 lanes take the
     // driver's 20-tick launch from 2.52-2.56 to 2.48-2.50 us per tick (median
     // of 30 regions, three passes; profiles/r06p_k20_block_ab.jsonl)
-    if (e->multi_block == 256 || (e->multi_block < 0 && e->multi_prefetch <= 0)) {
-      const dim3 g((unsigned)((e->n + 255) / 256));
-      if (pk)
-        err = pol == 1 ? launch_timed(k_step_multi<1, true, 256>, g, dim3(256), hs, e0, e1, a, e->dcfg, early)
-                       : launch_timed(k_step_multi<0, true, 256>, g, dim3(256), hs, e0, e1, a, e->dcfg, early);
-      else
-        err = pol == 1 ? launch_timed(k_step_multi<1, false, 256>, g, dim3(256), hs, e0, e1, a, e->dcfg, early)
-                       : launch_timed(k_step_multi<0, false, 256>, g, dim3(256), hs, e0, e1, a, e->dcfg, early);
-    } else {
-      const dim3 g(step_grid(e->n));
-      if (pk)
-        err = pol == 1
-                  ? launch_timed(k_step_multi<1, true, kStepBlock>, g, dim3(kStepBlock), hs, e0, e1, a, e->dcfg, early)
-                  : launch_timed(k_step_multi<0, true, kStepBlock>, g, dim3(kStepBlock), hs, e0, e1, a, e->dcfg, early);
-      // the prefetch wave only on request here (auto: none): 65,536 games
-      // 2.36 vs 2.33-2.39 us per tick at PF 1-4 and slower at 20 ticks per
-      // launch, where actions held in cache (an 8-slab ring) give 2.0
-      // (profiles/r04aq_prefetch_sweep.jsonl, r04at_prefetch_ring_sweep.jsonl)
-      else if (pol == 1 && e->multi_prefetch > 0 && n_ticks > 1 && e->n % 64 == 0)
-        err = e->multi_prefetch == 1
-                  ? launch_timed(k_step_multi<1, false, kStepBlock, 1>, g, dim3(kStepBlock + 64), hs, e0, e1, a,
-                                 e->dcfg, early)
-                  : e->multi_prefetch == 2
-                        ? launch_timed(k_step_multi<1, false, kStepBlock, 2>, g, dim3(kStepBlock + 64), hs, e0, e1,
-                                       a, e->dcfg, early)
-                        : launch_timed(k_step_multi<1, false, kStepBlock, 4>, g, dim3(kStepBlock + 64), hs, e0, e1,
-                                       a, e->dcfg, early);
-      else
-        err = pol == 1
-                  ? launch_timed(k_step_multi<1, false, kStepBlock>, g, dim3(kStepBlock), hs, e0, e1, a, e->dcfg,
-                                 early)
-                  : launch_timed(k_step_multi<0, false, kStepBlock>, g, dim3(kStepBlock), hs, e0, e1, a, e->dcfg,
-                                 early);
-    }
+    const bool four = e->multi_block == 256 || (e->multi_block < 0 && e->multi_prefetch <= 0);
+    // the feed wave only on request (auto: none), and only for the 88-B form
+    // on 64-lane workgroups through the write-through port: 65,536 games
+    // 2.36 vs 2.33-2.39 us per tick at PF 1-4 and slower at 20 ticks per
+    // launch, where actions held in cache (an 8-slab ring) give 2.0
+    // (profiles/r04aq_prefetch_sweep.jsonl, r04at_prefetch_ring_sweep.jsonl)
+    const int pf = (!four && !pk && pol == 1 && n_ticks > 1 && e->n % 64 == 0 && e->multi_prefetch > 0)
+                       ? e->multi_prefetch
+                       : 0;
+    if (four)
+      err = pk ? (pol == 1 ? launch_multi<1, true, 256>(pf, hs, a, e->dcfg, early)
+                           : launch_multi<0, true, 256>(pf, hs, a, e->dcfg, early))
+               : (pol == 1 ? launch_multi<1, false, 256>(pf, hs, a, e->dcfg, early)
+                           : launch_multi<0, false, 256>(pf, hs, a, e->dcfg, early));
+    else
+      err = pk ? (pol == 1 ? launch_multi<1, true, kStepBlock>(pf, hs, a, e->dcfg, early)
+                           : launch_multi<0, true, kStepBlock>(pf, hs, a, e->dcfg, early))
+               : (pol == 1 ? launch_multi<1, false, kStepBlock>(pf, hs, a, e->dcfg, early)
+                           : launch_multi<0, false, kStepBlock>(pf, hs, a, e->dcfg, early));
   }
   if (err != hipSuccess) return fail(SK_EHIP, std::string("k_step_multi launch: ") + hipGetErrorString(err));
   e->parity ^= 1;

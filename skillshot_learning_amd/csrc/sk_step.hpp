@@ -80,11 +80,7 @@ __device__ __forceinline__ void wave_sum4_u32(const unsigned in[4], uint64_t out
 // the slot line at `slot` (NULL: no counting)
 __device__ __forceinline__ WaveCtr ctr_load_at(const sk_counters* slot) {
   WaveCtr w;
-#ifdef SK_CTR_NOMEM  // timing ablation: counting without its memory traffic
-  w.v = make_ulonglong4(0, 0, 0, 0);
-#else
   w.v = slot ? *reinterpret_cast<const ulonglong4*>(slot) : make_ulonglong4(0, 0, 0, 0);
-#endif
   return w;
 }
 template <int BLK = kStepBlock>
@@ -105,10 +101,6 @@ __device__ __forceinline__ void ctr_settle(WaveCtr& w) {
 
 __device__ __forceinline__ void ctr_store_at(sk_counters* slot, const WaveCtr& w, uint64_t dones, uint64_t h1,
                                              uint64_t h2, uint64_t tsum) {
-#ifdef SK_CTR_NOMEM
-  asm volatile("" ::"s"(dones + h1 + h2 + tsum));
-  return;
-#endif
   if ((threadIdx.x & 63) == 0)
     *reinterpret_cast<ulonglong4*>(slot) = make_ulonglong4(w.v.x + dones, w.v.y + h1, w.v.z + h2, w.v.w + tsum);
 }
@@ -172,16 +164,13 @@ __device__ __forceinline__ void step_advance(const StepRef& s, uint64_t base, ui
 // The action slab is read once per tick (the actor's output or a pre-generated
 // random-policy slab): nontemporal (streaming) loads.  At 65,536 games with
 // the slab streamed from HBM the tick takes 4.74 instead of 4.93 us
-// (profiles/r01x_act_nt_ab.jsonl, three alternating passes).
+// (profiles/r01x_act_nt_ab.jsonl, three alternating passes); in the multi-tick
+// kernels plain loads were no gain (profiles/r04bc_act_nt_multi_ab.jsonl).
 __device__ __forceinline__ float2 load_action(const float2* p) {
-#ifdef SK_ACT_PLAIN  // A/B build only (multi-tick kernels: no gain, profiles/r04bc_act_nt_multi_ab.jsonl)
-  return *p;
-#else
   float2 v;
   v.x = __builtin_nontemporal_load(&p->x);
   v.y = __builtin_nontemporal_load(&p->y);
   return v;
-#endif
 }
 
 // ------------------------------------------------------------------ kernels
@@ -317,11 +306,6 @@ __device__ __forceinline__ StepLane split_load(const StepArgs& a, int64_t gt, sk
   return L;
 }
 
-// SK_SPLIT_FINISH_BF = 0 (A/B builds): the round-5 branches and one store
-// pass after the restart
-#ifndef SK_SPLIT_FINISH_BF
-#define SK_SPLIT_FINISH_BF 1
-#endif
 __device__ __forceinline__ void split_finish(const StepArgs& a, const Cfg& c, const StepLane& L, float2 act,
                                              sk_counters* slot) {
   const int64_t i = L.i, h = L.h;
@@ -356,9 +340,8 @@ __device__ __forceinline__ void split_finish(const StepArgs& a, const Cfg& c, co
     }
   }
   const double q_old = qrot;
-#if SK_SPLIT_FINISH_BF
-  // round 6: the commits as selects (split_tick_carry's form: the tick is a
-  // latency chain and exec-mask branches serialise it)
+  // the commits as selects (split_tick_carry's form: the tick is a latency
+  // chain and exec-mask branches serialise it)
   {
     const double speed = clamp_action((double)act.x), psp = (double)c.pspeed;  // Player.py:57-68
     const double nxf = __builtin_rint((double)px - (m.s * psp) * speed);
@@ -402,26 +385,10 @@ __device__ __forceinline__ void split_finish(const StepArgs& a, const Cfg& c, co
     winner = h1 ? 1 : (h2 ? 2 : winner);
     live = (h1 || h2) ? 0 : live;
   }
-#else
-  move_direction_sc(c, px, py, m, (double)act.x);
-  rot = rn;
-  shoot_s(c, px, py, rot, qx, qy, qrot, qcd, qage, qvalid);
-  // game_tick  SkillshotGame.py:115-122 (live is identical in both lanes)
-  if (live) {
-    ticks += 1;
-    projectile_tick_sc(c, qx, qy, t, qcd, qage, qvalid);
-  }
-  const int opx = pair_swap(px), opy = pair_swap(py);
-  const int oqx = pair_swap(qx), oqy = pair_swap(qy), oqv = pair_swap(qvalid);
-  if (live) {
-    if (p == 0) collide_s(c, px, py, qx, qy, qvalid, opx, opy, oqx, oqy, oqv, live, winner);
-    else collide_s(c, opx, opy, oqx, oqy, oqv, px, py, qx, qy, qvalid, live, winner);
-  }
-#endif
   ctr_settle(wc);  // every load consumed, no state store issued yet
-#if SK_SPLIT_FINISH_BF
   // the state out before the obs, the ring row and the restart (k_step_multi's
-  // SK_EARLY_STORE); a restarted game's lanes store theirs again below
+  // early store, for its reason); a restarted game's lanes store theirs again
+  // below
   if (in) {
     reinterpret_cast<int2*>(a.v.pos)[h] = make_int2(px, py);
     reinterpret_cast<double*>(a.v.rot)[h] = rot;
@@ -434,9 +401,6 @@ __device__ __forceinline__ void split_finish(const StepArgs& a, const Cfg& c, co
       a.v.misc[i] = make_int2(ticks, (int)f);
     }
   }
-#else
-  (void)q_old;
-#endif
   const bool d = in && ((!live) || (ticks >= a.tick_limit));  // SkillshotLearner.py:302
   const bool want_obs = a.obs || a.reward || a.obs_reset;     // launch-uniform
   float o[12];
@@ -444,12 +408,7 @@ __device__ __forceinline__ void split_finish(const StepArgs& a, const Cfg& c, co
   double gq = 0.0;  // the fast projectile gradient (the ambiguous flag's interval check)
   if (in && want_obs) {
     float pd;
-#ifdef SK_ABL_NOOBS  // timing ablation only: obs values without their arithmetic
-    for (int k = 0; k < 12; ++k) o[k] = (float)(px + k * qx) + pr.s * (float)t.c;
-    pd = o[3];
-#else
     obs12_sc(c, px, py, rot, pr, qx, qy, qrot, t, qcd, qvalid, opx, opy, o, &pd, &amb, &gq);
-#endif
     if (a.obs) store_obs(a.obs, a.n, p, i, o);
     if (a.reward) {
       float r;
@@ -510,7 +469,7 @@ __device__ __forceinline__ void split_finish(const StepArgs& a, const Cfg& c, co
     store_obs(a.obs_reset, a.n, p, i, o);
   }
   const int ov = pair_swap(qvalid);
-  if (!SK_SPLIT_FINISH_BF || reset) {
+  if (reset) {
     reinterpret_cast<int2*>(a.v.pos)[h] = make_int2(px, py);
     reinterpret_cast<double*>(a.v.rot)[h] = rot;
     reinterpret_cast<int2*>(a.v.qpos)[h] = make_int2(qx, qy);
