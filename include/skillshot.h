@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define SK_ABI_VERSION 11
+#define SK_ABI_VERSION 12
 
 enum {
   SK_OK = 0,
@@ -717,6 +717,33 @@ int sk_fit_actor_f32(float* actor_flat, float* adam_m, float* adam_v, float* ste
                      const float* critic_flat, const float* states, int32_t n_minibatches, float lr, float beta1,
                      float beta2, float eps, void* xbuf, uint64_t* epoch, uint32_t* timeout, float* zbuf,
                      void* stream);
+
+/* --- boards (ABI 12) ----------------------------------------------------- */
+
+/* SkillshotGame.get_board (SkillshotGame.py:36-56) for m games in ONE launch:
+ * out uint8[m][board_w][board_h], [x][y] indexing, boards back to back, 16-byte
+ * aligned; board k shows game ids[k] (int64[m], any order, repeats allowed;
+ * NULL: games 0 .. m-1).  Values: 0 empty, 1 / 2 the players' bodies (the inner
+ * 3x3 of the 5x5 sprite), 3 / 4 their pointer cell and their valid projectile
+ * (the 3x3 X).  The painter's order, last writer wins: p1 body, p1 pointer, p1
+ * projectile, p2 body, p2 pointer, p2 projectile.  The pointer cell of the 5x5
+ * is (floor(-sin(rot) * 5 / 2 + 5 / 2), floor(-cos(rot) * 5 / 2 + 5 / 2)) in
+ * fp64; it is not drawn when either index is 5 (or the rotation is not
+ * finite).  Cells outside the board are clipped (the reference would raise or
+ * wrap: only loaded states reach them), an invalid projectile is never drawn,
+ * and an id outside [0, n_envs) gives an all-zero board.  Every output byte is
+ * written exactly once; no allocation, no sync: capturable.  SK_EINVAL for a
+ * NULL env / view / plane / out, m < 0, out not 16-byte aligned, device planes
+ * not 16-byte (misc: 8-byte) aligned, player_size != 5 or projectile_size !=
+ * 3 (the sprite images are the reference's fixed ones), or a board of 2^31
+ * cells or more; m == 0 is a successful no-op.
+ * sk_render_states renders caller-owned planes (e.g. a recorded trace of one
+ * game, view->n_envs states) on `device` (-1: the CPU backend, host pointers;
+ * else the current HIP device's pointers); cfg NULL = the reference values.
+ * sk_env_render is sk_render_states over the env's own state. */
+int sk_render_states(const sk_config* cfg, int32_t device, const sk_state_view* view, const int64_t* ids, int64_t m,
+                     uint8_t* out, void* stream);
+int sk_env_render(sk_env* env, const int64_t* ids, int64_t m, uint8_t* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,7 +16,7 @@ from . import build as _build
 
 SK_OK, SK_EINVAL, SK_EHIP, SK_ENOMEM, SK_ENODEV = 0, -1, -2, -3, -4
 SK_REWARD_LOOKING, SK_REWARD_SIMPLE = 0, 1
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 # every symbol include/skillshot.h declares
 EXPORTS = (
@@ -37,6 +37,7 @@ EXPORTS = (
     "sk_critic_grad_bootstrap_sampled", "sk_actor_grad_f32", "sk_actor_grad_f32_step",
     "sk_critic_grad_f32_sampled_step", "sk_critic_grad_f32_step", "sk_replay_sample_excl",
     "sk_fit_xbuf_bytes", "sk_fit_critic_f32", "sk_fit_actor_f32",
+    "sk_render_states", "sk_env_render",
 )
 
 
@@ -178,6 +179,8 @@ def load(build_if_missing=True):
         "sk_fit_xbuf_bytes": ([], ctypes.c_size_t),
         "sk_fit_critic_f32": ([P, P, P, P, i32, P, P, P, i32, u64, P, f32, f32, f32, f32, P, P, P, P, P], ctypes.c_int),
         "sk_fit_actor_f32": ([P, P, P, P, i32, P, P, i32, f32, f32, f32, f32, P, P, P, P, P], ctypes.c_int),
+        "sk_render_states": ([ctypes.POINTER(SkConfig), i32, ctypes.POINTER(SkStateView), P, i64, P, P], ctypes.c_int),
+        "sk_env_render": ([P, P, i64, P, P], ctypes.c_int),
     }
     for name, (argt, rest) in sig.items():
         fn = getattr(L, name)

@@ -1520,6 +1520,10 @@ static hipError_t launch_multi(int pf, hipStream_t hs, const MultiArgs& a, const
   return launch(k_step_multi<POL, PACK, BLK>, g, dim3(BLK), hs, a, c, early);
 }
 
+// the board rasteriser's launch (sk_render.hip)
+hipError_t sk_render_launch(const sk_config& cfg, const sk_state_view& view, const int64_t* ids, int64_t m,
+                            uint8_t* out, hipStream_t stream);
+
 // ------------------------------------------------------------------ host ABI
 extern "C" {
 
@@ -2382,6 +2386,40 @@ int sk_env_rollout_random(sk_env* e, int32_t n_ticks, int32_t tick_limit, void* 
   SK_LAUNCH_CHECK();
   e->parity ^= 1;
   return SK_OK;
+}
+
+int sk_render_states(const sk_config* cfg, int32_t device, const sk_state_view* view, const int64_t* ids, int64_t m,
+                     uint8_t* out, void* stream) {
+  if (!view) return fail(SK_EINVAL, "view is NULL");
+  if (!out) return fail(SK_EINVAL, "out is NULL");
+  if (m < 0) return fail(SK_EINVAL, "m must be >= 0");
+  if (((uintptr_t)out) & 15) return fail(SK_EINVAL, "out must be 16-byte aligned");
+  sk_config c;
+  if (cfg) c = *cfg; else sk_config_default(&c);
+  if (c.board_w <= 0 || c.board_h <= 0 || (int64_t)c.board_w * c.board_h > 0x7fffffff)
+    return fail(SK_EINVAL, "board_w x board_h must be in 1 .. 2^31 - 1 cells");
+  if (c.player_size != 5 || c.projectile_size != 3)
+    return fail(SK_EINVAL, "the board's sprites are the reference's: player_size 5, projectile_size 3");
+  if (view->n_envs < 0 || !view->pos || !view->rot || !view->qpos || !view->qrot || !view->qcdage || !view->misc)
+    return fail(SK_EINVAL, "incomplete sk_state_view");
+  if (m == 0) return SK_OK;
+  if (m > INT64_MAX / ((int64_t)c.board_w * c.board_h)) return fail(SK_EINVAL, "m boards overflow int64 bytes");
+  if (device == -1) return skh::render(c, *view, ids, m, out), SK_OK;
+  if (device < 0) return fail(SK_EINVAL, "device index out of range");
+  for (const void* p : {(const void*)view->pos, (const void*)view->rot, (const void*)view->qpos,
+                        (const void*)view->qrot, (const void*)view->qcdage})
+    if (((uintptr_t)p) & 15) return fail(SK_EINVAL, "state planes must be 16-byte aligned");
+  if (((uintptr_t)view->misc) & 7) return fail(SK_EINVAL, "misc plane must be 8-byte aligned");
+  if (((uintptr_t)ids) & 7) return fail(SK_EINVAL, "ids must be 8-byte aligned");
+  const hipError_t err = sk_render_launch(c, *view, ids, m, out, (hipStream_t)stream);
+  if (err == hipErrorInvalidValue) return fail(SK_EINVAL, "too many boards for one launch");
+  HIP_TRY(err);
+  return SK_OK;
+}
+
+int sk_env_render(sk_env* e, const int64_t* ids, int64_t m, uint8_t* out, void* stream) {
+  SK_CHECK_ENV(e);
+  return sk_render_states(&e->cfg, e->device, &e->hview, ids, m, out, stream);
 }
 
 }  // extern "C"

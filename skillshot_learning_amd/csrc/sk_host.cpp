@@ -568,4 +568,38 @@ void rollout_random(Host& h, int n_ticks, int tick_limit) {
   });
 }
 
+// SkillshotGame.get_board (SkillshotGame.py:36-56): the painter, in its order,
+// on a zeroed board; cells off the board are clipped.  The sprite images are
+// the reference's fixed ones (Player.py:9-13 5x5 with the inner 3x3 set,
+// Projectile.py:5-7 the 3x3 X).
+void render(const sk_config& cfg, const sk_state_view& v, const int64_t* ids, int64_t m, uint8_t* out) {
+  const int64_t W = cfg.board_w, H = cfg.board_h;
+  for (int64_t k = 0; k < m; ++k) {
+    uint8_t* b = out + k * W * H;
+    std::memset(b, 0, (size_t)(W * H));
+    const int64_t g = ids ? ids[k] : k;
+    if (g < 0 || g >= v.n_envs) continue;
+    const auto put = [&](int64_t x, int64_t y, uint8_t c) {
+      if (x >= 0 && x < W && y >= 0 && y < H) b[x * H + y] = c;
+    };
+    const uint32_t flags = (uint32_t)v.misc[2 * g + 1];
+    for (int p = 0; p < 2; ++p) {
+      const int64_t px = v.pos[4 * g + 2 * p], py = v.pos[4 * g + 2 * p + 1];
+      const double rot = v.rot[2 * g + p];
+      for (int iy = 1; iy <= 3; ++iy)
+        for (int ix = 1; ix <= 3; ++ix) put(px + ix, py + iy, (uint8_t)(1 + p));
+      // math.floor(-math.sin(rot) * 5 / 2 + 5 / 2): index 5 (sin or cos = -1) matches no cell
+      const double fx = std::floor(((-std::sin(rot)) * 5.0) / 2.0 + 2.5);
+      const double fy = std::floor(((-std::cos(rot)) * 5.0) / 2.0 + 2.5);
+      if (fx >= 0.0 && fx <= 4.0 && fy >= 0.0 && fy <= 4.0) put(px + (int)fx, py + (int)fy, (uint8_t)(3 + p));
+      if ((flags >> (8 * p)) & 0xff) {
+        const int64_t qx = v.qpos[4 * g + 2 * p], qy = v.qpos[4 * g + 2 * p + 1];
+        for (int iy = 0; iy < 3; ++iy)
+          for (int ix = 0; ix < 3; ++ix)
+            if (((ix ^ iy) & 1) == 0) put(qx + ix, qy + iy, (uint8_t)(3 + p));
+      }
+    }
+  }
+}
+
 }  // namespace skh

@@ -946,18 +946,22 @@ class SkillshotLearner:
         call = dict(epoch_ticks=[], epoch_winner=[], epoch_board_sequences=[])
         # the episodes on device in one launch (sk_env_act_episode) where the
         # fp32 acting kernel runs them; the per-tick loop below otherwise
-        # (bf16 / torch actors, the full reward's per-tick features, boards)
-        on_device = (not full and not save_boards and self.actor_kernel is not None and
+        # (bf16 / torch actors, the full reward's per-tick features).  Boards
+        # stay on the device path: board_game's episode is replayed from its
+        # recorded actions and rendered in one launch (_episode_boards)
+        on_device = (not full and self.actor_kernel is not None and
                      getattr(self.actor_kernel, "fused_act_step", False) and self.n_envs % 4 == 0 and
                      os.environ.get("SK_EPISODE_KERNEL", "1") != "0")
         for _ in range(epochs):
             g.reset(random_positions=self.use_random_start)
             obs = self.prepare_states()
             if on_device:
-                ticks, winner = self._episode_on_device(obs, reward)
+                ticks, winner = self._episode_on_device(obs, reward, board_game if save_boards else None)
                 for d in (self.progress, call):
                     d["epoch_ticks"].append(ticks.cpu())
                     d["epoch_winner"].append(winner.cpu())
+                if save_boards:
+                    call["epoch_board_sequences"].append(self._episode_boards())
                 continue
             alive = torch.ones(self.n_envs, dtype=torch.bool, device=self.device)
             S, A, R, K, FT, W = [], [], [], [], [], []
@@ -1008,13 +1012,18 @@ class SkillshotLearner:
             self.save_training_boards(call["epoch_board_sequences"])
         return self.progress
 
-    def _episode_on_device(self, obs, reward):
+    def _episode_on_device(self, obs, reward, board_game=None):
         """one model_train epoch with the episodes collected in one launch
         (VecSkillshotGame.act_episode: every game until it ends, the actor
         fixed, fresh noise per tick), then models_fit on the played rows in
         the per-tick loop's order (tick, player, game).  Returns the games'
-        final ticks and winners."""
+        final ticks and winners.  board_game: also keep that game's start
+        state and the actions it played (for _episode_boards)."""
         g = self.game_environment
+        if board_game is not None:
+            from .vec_env import PLANES
+            start = {name: getattr(g, name)[board_game].clone() for name, _, _ in PLANES}
+            played = []
         mode = self.exploration
         kw = dict(noise_sd=self.param_noise_sd if mode == "param_noise" else 0.0,
                   action_sd=self.action_noise_sd if mode == "action_noise" else 0.0, reward=reward)
@@ -1029,7 +1038,11 @@ class SkillshotLearner:
             ep = g.act_episode(self.actor_kernel, obs, n_ticks=C, out=getattr(self, "_episode_bufs", None), **kw)
             self._episode_bufs = ep
             lengths = ep["lengths"].long()
-            T = int(lengths.max()) if self.n_envs else 0
+            if board_game is not None:  # one host read for both lengths
+                T, tb = torch.stack((lengths.max(), lengths[board_game])).tolist()
+                played.append(ep["actions"][:tb, :, board_game].clone())
+            else:
+                T = int(lengths.max()) if self.n_envs else 0
             keep = (torch.arange(T, device=self.device)[:, None] < lengths[None, :])[:, None, :].expand(
                 T, 2, self.n_envs)
             S.append(ep["states"][:T][keep])
@@ -1039,7 +1052,19 @@ class SkillshotLearner:
                 break
             obs = ep["states"][C]
         self.models_fit(torch.cat(S), torch.cat(A), torch.cat(R))
+        if board_game is not None:
+            self._episode_trace = (start, torch.cat(played))
         return g.ticks.clone(), g.winner_id.clone()
+
+    def _episode_boards(self):
+        """the board after each tick the last on-device episode's board game
+        was live (:315-317), int8 [ticks, W, H]: what the per-tick loop's
+        get_board calls collect, from a host replay of the recorded actions
+        (VecSkillshotGame.trace_game) and one render_states launch"""
+        g = self.game_environment
+        start, actions = self._episode_trace
+        boards = g.render_states(g.trace_game(start, actions))
+        return boards.to(torch.int8).cpu().numpy()
 
     def episode_chunk_ticks(self, share=0.125):
         """ticks per episode launch: the tick limit, or fewer where the

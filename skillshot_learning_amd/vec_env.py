@@ -156,6 +156,94 @@ class VecSkillshotGame:
         return rasterize_board(np.zeros((250, 250), dtype=np.int64), [pos[0:2], pos[2:4]], rot,
                                [qpos[0:2], qpos[2:4]], [flags & 0xFF, (flags >> 8) & 0xFF])
 
+    def _board_out(self, m, out):
+        shape = (m, self.config.board_w, self.config.board_h)
+        if out is None:
+            return torch.empty(shape, dtype=torch.uint8, device=self.device)
+        if (out.dtype != torch.uint8 or out.device != self.device or tuple(out.shape) != shape or
+                not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous uint8 tensor {shape} on {self.device}")
+        return out
+
+    def render(self, ids=None, out=None):
+        """SkillshotGame.get_board (SkillshotGame.py:36-56) of many games in
+        one launch (sk_env_render) on torch's current stream: uint8
+        [M, board_w, board_h], [x, y] indexing, values 0..4 (get_board stays
+        the reference's int64 host view of one game).  ids: None (every game,
+        M = n_envs), a Python / numpy sequence of game indices (checked here:
+        IndexError outside [0, n_envs)) or an int64 tensor on this device
+        (not checked: an index out of range gives an all-zero board); any
+        order, repeats allowed.  out: a contiguous uint8 [M, W, H] tensor on
+        this device, 16-byte aligned.  Cells off the board are clipped and an
+        invalid projectile is not drawn."""
+        if ids is None:
+            idx, m = None, self.n
+        elif torch.is_tensor(ids):
+            if ids.dtype != torch.int64 or ids.device != self.device or ids.dim() != 1:
+                raise ValueError(f"ids must be a 1-d int64 tensor on {self.device}")
+            idx, m = ids.contiguous(), ids.numel()
+        else:
+            a = np.asarray(ids)
+            if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+                raise ValueError("ids must be a 1-d sequence of integers")
+            a = a.astype(np.int64)
+            if a.size and (a.min() < 0 or a.max() >= self.n):
+                raise IndexError(f"game index out of range [0, {self.n})")
+            idx, m = torch.from_numpy(a).to(self.device), a.size
+        o = self._board_out(m, out)
+        if m:
+            check(self._L.sk_env_render(self._h, _ptr(idx), m, _ptr(o), self._stream()))
+        return o
+
+    def render_states(self, planes, out=None):
+        """`render` of caller-owned states (sk_render_states), e.g. one game's
+        recorded trace: planes maps every PLANES name to a tensor [L, width]
+        on this device in the engine's layout; returns uint8 [L, W, H], one
+        launch."""
+        ts = []
+        for name, dt, w in PLANES:
+            t = torch.as_tensor(planes[name])
+            if t.device != self.device:
+                raise ValueError(f"plane {name} must be on {self.device}")
+            ts.append(t.to(dt).reshape(-1, w).contiguous())
+        m = ts[0].shape[0]
+        if any(t.shape[0] != m for t in ts):
+            raise ValueError("planes must hold the same number of states")
+        o = self._board_out(m, out)
+        if m:
+            view = _capi.SkStateView(m, *[t.data_ptr() for t in ts])
+            check(self._L.sk_render_states(ctypes.byref(self.config), -1 if self.is_cpu else self.device.index,
+                                           ctypes.byref(view), None, m, _ptr(o), self._stream()))
+        return o
+
+    def trace_game(self, start_planes_row, actions):
+        """One game's states after each tick of a recorded episode: the game
+        starts from start_planes_row (every PLANES name -> its row of one
+        game, [width]) and acts on actions float32 [L, 2, 2] (tick, player,
+        {speed, look}), replayed on a one-game CPU-backend env with this env's
+        config and tick limit and no auto-reset; the replay stops when the
+        game ends.  Returns planes {name: [T, width]}, T <= L, on this env's
+        device.  Exact: the CPU backend's step equals the device step bit
+        for bit, and the device's multi-tick launches equal its per-tick
+        step."""
+        acts = torch.as_tensor(actions).detach().to("cpu", torch.float32).reshape(-1, 2, 1, 2)
+        g = getattr(self, "_trace_env", None)
+        if g is None:
+            g = self._trace_env = VecSkillshotGame(1, device="cpu", seed=self.seed, tick_limit=self.tick_limit,
+                                                   random_positions=False, config=self.config)
+        g.tick_limit = self.tick_limit
+        g.load_state_dict({name: torch.as_tensor(start_planes_row[name]).detach().cpu().numpy()
+                           for name, _, _ in PLANES})
+        rec = {name: [] for name, _, _ in PLANES}
+        for a in acts:
+            done = g.step(a, obs=False, auto_reset=False)["done"]
+            for name, _, _ in PLANES:
+                rec[name].append(getattr(g, name)[0].clone())
+            if bool(done[0]):
+                break
+        return {name: (torch.stack(rec[name]) if rec[name] else torch.empty((0, w), dtype=dt)).to(self.device)
+                for name, dt, w in PLANES}
+
     # convenience decoded views -------------------------------------------
     @property
     def ticks(self):
