@@ -17,7 +17,10 @@
 //                         action slab a tick ahead in registers or through a
 //                         feed wave and LDS
 //     k_step_split_multi  two lanes per game, step-only or with obs / reward;
-//                         optionally an action-slab prefetch wave
+//                         optionally an action-slab prefetch wave; step-only
+//                         also with the packed 48-B form between ticks (8 B
+//                         per player and plane), the default from 40,960 to
+//                         98,304 games
 //     both run the carried-sincos tick: tick_env_carry (sk_device.hpp) and
 //     split_tick_carry (below)
 //   k_rollout_random      n ticks of the random policy in one launch, state
@@ -73,10 +76,11 @@ struct sk_env {
   int multi_stagger;  // waves 4-7 of a 512-lane workgroup start this x 512 cycles late (SK_MULTI_STAGGER)
   int multi_prefetch; // action-slab prefetch wave, ticks ahead (SK_MULTI_PREFETCH; 0 off, -1 auto): k_step_multi
                       // (64-lane, 88-B form) and k_step_split_multi
-  // k_step_multi's packed resident form between ticks: -1 auto (above one
-  // wave per SIMD), 1 / 0 force (SK_MULTI_PACK)
+  // the packed resident form between ticks (k_step_multi, step-only
+  // k_step_split_multi): -1 auto (above one wave per SIMD), 1 / 0 force
+  // (SK_MULTI_PACK)
   int multi_pack;
-  char* d_pack;  // its scratch (48 B x n), allocated at the first multi-tick launch
+  char* d_pack;  // its scratch (48 B x n): make_env for the sizes that pack by default, else the first packed launch
   // device = -1: the CPU backend (sk_host.cpp) owns the games; every entry
   // point below forwards to it and takes host pointers
   skh::Host* host;
@@ -107,12 +111,26 @@ static constexpr int64_t kFastStepMaxEnvs = 786432;
 static constexpr int64_t kSplitStepMaxEnvs = 8192;
 static constexpr int64_t kEarlyDrawMinEnvs = 32768;
 // k_step_multi's packed resident form above this many games (one wave per
-// SIMD on 1,024 SIMDs)
+// SIMD on 1,024 SIMDs).  By default the lane-per-game kernel runs only above
+// kSplitPackMaxEnvs; this bound is what SK_MULTI_SPLIT=0 leaves in force
 constexpr int64_t kPackMinEnvs = 65536;
-// k_step_multi: two lanes per game up to this many games.  Write-through
-// port, 400 ticks per launch: 8,192 games 1.59 vs 1.85 us per tick, 32,768
-// 1.80 vs 2.02, but 65,536 2.59 vs 2.36 (profiles/r03c_multi_split_sweep.jsonl)
+// k_step_multi: two lanes per game with the 88-B form up to this many games.
+// Write-through port, 400 ticks per launch: 8,192 games 1.59 vs 1.85 us per
+// tick, 32,768 1.80 vs 2.02, but 65,536 2.59 vs 2.36
+// (profiles/r03c_multi_split_sweep.jsonl); these sizes run the PACK = false
+// instantiations, which the packed one left as they were
 static constexpr int64_t kSplitMultiMaxEnvs = 32768;  // k_step: restart draw under the loads
+// k_step_split_multi's packed instantiation (two or three waves per SIMD over
+// 48 B per game and tick, 64-lane workgroups) for this range of games.
+// Write-through port, 400 ticks per launch, us per tick against the default
+// before it (k_step_multi: the 88-B form up to 65,536 games, packed above):
+// 40,960 games 1.73-1.75 vs 1.79-1.84, 49,152 1.75-1.76 vs 1.81-1.82, 57,344
+// 1.78-1.79 vs 2.00, 65,536 1.80-1.81 vs 2.02-2.09, 81,920 2.19-2.21 vs
+// 2.87-2.89, 98,304 2.23-2.26 vs 2.91-2.95; but 114,688 3.25-3.31 vs
+// 3.06-3.08 and 131,072 3.33-3.35 vs 3.07-3.13: from there k_step_multi's
+// packed form (profiles/r08_split_pack_boundary.jsonl)
+static constexpr int64_t kSplitPackMinEnvs = 40960;
+static constexpr int64_t kSplitPackMaxEnvs = 98304;
 // SK_CTR_STRIDE slots per wave of the widest step grid (k_step_split: two
 // lanes per game), at least SK_COUNTER_SLOTS
 static inline int64_t counter_slots(int64_t n) {
@@ -727,7 +745,7 @@ __device__ __forceinline__ void multi_compute(const MultiArgs& a, const Cfg& c, 
   // the sincos carried from the previous tick (tick_env_carry, sk_device.hpp)
   tick_env_carry(c, e, tc, L.in, acts[0].x, acts[0].y, acts[1].x, acts[1].y);
   SK_MTW(tick, 2);
-  // The 88-B form stores early: the state goes out right after the tick,
+  // The state goes out right after the tick (early store),
   // before the done outputs and the restart; a lane that restarts stores its
   // planes again (its later stores win: same wave, same addresses, issue
   // order).  The stores then drain while the wave finishes the tick instead
@@ -735,9 +753,29 @@ __device__ __forceinline__ void multi_compute(const MultiArgs& a, const Cfg& c, 
   // us per tick at 400 ticks per launch, 2.6 -> 2.5 at 20; profiles/r06n_*).
   // Storing pos / rot / qrot earlier still, between do_actions and game_tick,
   // was slower (2.02 -> 2.13, 2.54 -> 2.59; profiles/r06o_*).
-  constexpr bool EARLY = !PACK;
-  if constexpr (EARLY) {
-    if (L.in) store_env_port<POL>(a, r, L.i, e, q_old0, q_old1, packed);
+  // The packed form stores early too (round 8; it had stored after the
+  // restart): the pack decision is taken here, on the post-tick state (a
+  // restart state always fits: the host checks the configuration's restart
+  // positions).  114,688 games 3.00-3.03 vs 3.12-3.19 us per tick at 400
+  // ticks per launch, 3.21-3.24 vs 3.42-3.48 at 20; 131,072 3.05-3.06 vs
+  // 3.09-3.19; 262,144 5.17-5.40 vs 5.55-5.73 and 5.64-5.67 vs 6.00-6.15
+  // (profiles/r08_lane_pack_early_ab.jsonl)
+  bool to_pack = false;
+  if constexpr (PACK) {
+    const bool fit =
+        !L.in || ((int)pack_fits_player(e.px[0], e.py[0], e.qx[0], e.qy[0], e.qcd[0], e.qage[0], e.qvalid[0]) &
+                  (int)pack_fits_player(e.px[1], e.py[1], e.qx[1], e.qy[1], e.qcd[1], e.qage[1], e.qvalid[1]) &
+                  (int)pack_fits_game(e.ticks, e.live, e.winner));
+    to_pack = a.pack != nullptr && !last && __ballot(!fit) == 0;  // wave-uniform
+  }
+  if (L.in) {
+    if (PACK && to_pack) {
+      const bool qch = !packed || (__double_as_longlong(e.qrot[0]) != __double_as_longlong(q_old0)) ||
+                       (__double_as_longlong(e.qrot[1]) != __double_as_longlong(q_old1));
+      store_env_pack<POL>(a, rp, L.i, e, qch);
+    } else {
+      store_env_port<POL>(a, r, L.i, e, q_old0, q_old1, packed);
+    }
   }
   // every load of this tick consumed (the counter slot's, issued first, with
   // them): without this the waitcnt pass, its tracking lost across the loop,
@@ -762,24 +800,9 @@ __device__ __forceinline__ void multi_compute(const MultiArgs& a, const Cfg& c, 
   }
   if (!last) carry_note(tc, e);
   SK_MTW(tick, 3);
-  bool to_pack = false;
-  if constexpr (PACK) {
-    const bool fit =
-        !L.in || ((int)pack_fits_player(e.px[0], e.py[0], e.qx[0], e.qy[0], e.qcd[0], e.qage[0], e.qvalid[0]) &
-                  (int)pack_fits_player(e.px[1], e.py[1], e.qx[1], e.qy[1], e.qcd[1], e.qage[1], e.qvalid[1]) &
-                  (int)pack_fits_game(e.ticks, e.live, e.winner));
-    to_pack = a.pack != nullptr && !last && __ballot(!fit) == 0;  // wave-uniform
-  }
-  if constexpr (EARLY) {
-    if (d && a.auto_reset) store_env_port<POL>(a, r, L.i, e, q_old0, q_old1, true);  // the restarted game
-  } else if (L.in) {
-    if (PACK && to_pack) {
-      const bool qch = !packed || (__double_as_longlong(e.qrot[0]) != __double_as_longlong(q_old0)) ||
-                       (__double_as_longlong(e.qrot[1]) != __double_as_longlong(q_old1));
-      store_env_pack<POL>(a, rp, L.i, e, qch);
-    } else {
-      store_env_port<POL>(a, r, L.i, e, q_old0, q_old1, packed);
-    }
+  if (d && a.auto_reset) {  // the restarted game
+    if (PACK && to_pack) store_env_pack<POL>(a, rp, L.i, e, true);
+    else store_env_port<POL>(a, r, L.i, e, q_old0, q_old1, true);
   }
   packed = to_pack;
 }
@@ -1010,10 +1033,11 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_multi(MultiArg
 // with pair_swap (DPP) for the collision test.  Twice the waves of
 // k_step_multi at half the dependent chain per lane: at 65,536 games two
 // waves share each SIMD, so one wave's state round trip through memory
-// overlaps the other's tick.  Same contract, same state ports; the 88-B form
-// every tick (the packed form compiled in cost the small grids a quarter of
-// their tick: 8,192 games 1.98 vs 1.59 us; profiles/r03f_multi_pack*_sweep.jsonl
-// vs r03c_multi_split_sweep.jsonl).
+// overlaps the other's tick.  Same contract, same state ports.  The packed
+// form is a compile-time instantiation (PACK), chosen by the host for
+// kSplitPackMinEnvs .. kSplitPackMaxEnvs games: as a runtime branch it cost
+// the small grids a quarter of their tick (8,192 games 1.98 vs 1.59 us;
+// profiles/r03f_multi_pack*_sweep.jsonl vs r03c_multi_split_sweep.jsonl).
 template <int POL>
 __device__ __forceinline__ void st_half_d(const MultiArgs& a, __amdgpu_buffer_rsrc_t r, int k, double* plane, int64_t h,
                                           double v) {
@@ -1094,21 +1118,81 @@ __device__ __forceinline__ void split_store_state(const MultiArgs& a, __amdgpu_b
   st_half_i<POL>(a, r, 4, reinterpret_cast<int2*>(a.v.qcdage), L.h, qcd, qage);
   if (L.p == 0) st_half_i<POL>(a, r, 5, a.v.misc, L.i, ticks, (int)f);
 }
+// The packed form in the split geometry (store_env_pack's layout: R double2[n],
+// Q double2[n], S int4[n]): lane 2i + p owns player p's 8-byte half of each
+// plane, the rotation, the projectile rotation and {pack_pos, pack_cah}.  The
+// high half of player 1's cah word is the game's ticks, of player 2's its
+// flag byte; the pair exchanges them with one pair_swap.  rp: the resource
+// over a.pack (POL 1).
+template <int POL>
+__device__ __forceinline__ void split_load_pack(const MultiArgs& a, __amdgpu_buffer_rsrc_t rp, const SplitLane& L,
+                                                SplitRaw& w) {
+  if constexpr (POL == 0) {
+    const skb2i* P = reinterpret_cast<const skb2i*>(a.pack);
+    w.rot = P[L.hc];
+    w.qrot = P[2 * a.n + L.hc];
+    w.pp = P[4 * a.n + L.hc];
+  } else {
+    const uint32_t o = (uint32_t)L.hc * 8u, plane = (uint32_t)a.n * 16u;
+    w.rot = __builtin_amdgcn_raw_buffer_load_b64(rp, o, 0, 16);
+    w.qrot = __builtin_amdgcn_raw_buffer_load_b64(rp, o + plane, 0, 16);
+    w.pp = __builtin_amdgcn_raw_buffer_load_b64(rp, o + 2u * plane, 0, 16);
+  }
+  w.ca = w.qq = w.mi = (skb2i){0, 0};
+  __builtin_amdgcn_sched_barrier(0);
+}
+template <int POL>
+__device__ __forceinline__ void split_store_pack(const MultiArgs& a, __amdgpu_buffer_rsrc_t rp, const SplitLane& L,
+                                                 double rot, double qrot, bool store_q, int pos, int cah) {
+  if constexpr (POL == 0) {
+    skb2i* P = reinterpret_cast<skb2i*>(a.pack);
+    P[L.h] = __builtin_bit_cast(skb2i, rot);
+    if (store_q) P[2 * a.n + L.h] = __builtin_bit_cast(skb2i, qrot);
+    P[4 * a.n + L.h] = (skb2i){pos, cah};
+  } else {
+    const uint32_t o = (uint32_t)L.h * 8u, plane = (uint32_t)a.n * 16u;
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(skb2i, rot), rp, o, 0, 16);
+    if (store_q) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(skb2i, qrot), rp, o + plane, 0, 16);
+    __builtin_amdgcn_raw_buffer_store_b64((skb2i){pos, cah}, rp, o + 2u * plane, 0, 16);
+  }
+}
 // OBS (the full contract, sk_env_step_multi_obs): the tick also evaluates
 // the exact sincos of the post-look rotation (the obs epilogue's projectile
 // sincos when it fires, and the next tick's carried move sincos: no
 // evaluation at the next tick's top) and the fp32 one (obs12_sc's `pr`), and
 // writes the observation and reward after the state stores.
-template <int POL, bool OBS>
+//
+// PACK (step-only): between the ticks of a launch the state lives in the
+// packed 48-B form (split_load_pack / split_store_pack) while every lane of
+// the wave fits it, as in multi_compute: `packed` (wave-uniform) says where
+// this tick's state is and is set for the next tick.  The decision is taken
+// on the post-tick state, before the early store (a restart state always
+// fits: the host checks the configuration's restart positions); the
+// launch's first tick loads and its last stores the exchange format, and a
+// tick that follows a packed one stores the qrot plane regardless.
+template <int POL, bool OBS, bool PACK = false>
 __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& c, __amdgpu_buffer_rsrc_t r,
                                                  SplitLane& L, WaveCtr& wc, int64_t so, uint64_t step,
-                                                 const SplitRaw& w, float2 act, SplitCarry& tc, bool last) {
+                                                 const SplitRaw& w, float2 act, SplitCarry& tc, bool last,
+                                                 __amdgpu_buffer_rsrc_t rp, bool& packed) {
+  static_assert(!(OBS && PACK), "the full contract never packs");
   using sktrig::round_safe;
   const int p = L.p;
   double rot = __builtin_bit_cast(double, w.rot), qrot = __builtin_bit_cast(double, w.qrot);
   int px = w.pp.x, py = w.pp.y, qx = w.qq.x, qy = w.qq.y, qcd = w.ca.x, qage = w.ca.y, ticks = w.mi.x;
   const unsigned flags = (unsigned)w.mi.y;
   int qvalid = (flags >> (8 * p)) & 0xff, live = (flags >> 16) & 0xff, winner = (flags >> 24) & 0xff;
+  if constexpr (PACK) {
+    if (packed) {  // w.pp: {pack_pos, pack_cah} of this lane's player
+      const unsigned s = (unsigned)w.pp.x, ch = (unsigned)w.pp.y;
+      px = s & 0xff; py = (s >> 8) & 0xff; qx = (s >> 16) & 0xff; qy = s >> 24;
+      qcd = (int)(signed char)(ch & 0xff); qage = (ch >> 8) & 0xff;
+      const unsigned hi = ch >> 16, ohi = (unsigned)pair_swap((int)hi);
+      const unsigned fl = p ? hi : ohi;
+      ticks = (int)(p ? ohi : hi);
+      qvalid = (fl >> p) & 1; live = (fl >> 2) & 1; winner = (fl >> 3) & 3;
+    }
+  }
   const double q_old = qrot;
   const bool f = qcd <= 0;  // fires this tick (Player.py:80)
   const bool miss = !tc.have || !same_bits(rot, tc.kr) || (qvalid && !f && !same_bits(qrot, tc.kq));
@@ -1202,10 +1286,20 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
     live = (h1 || h2) ? 0 : live;
   }
   ctr_settle(wc);  // every load of this tick consumed (see multi_tick)
-  {  // the state out before done / restart (multi_compute's early store, for its reason)
+  bool to_pack = false;
+  if constexpr (PACK) {
+    const bool fit = !L.in || ((int)pack_fits_player(px, py, qx, qy, qcd, qage, qvalid) &
+                               (int)pack_fits_game(ticks, live, winner));
+    to_pack = !last && __ballot(!fit) == 0;  // wave-uniform
+  }
+  if (PACK && to_pack) {  // the packed halves out before done / restart
+    const bool qch = !packed || __double_as_longlong(qrot) != __double_as_longlong(q_old);
+    const unsigned hi = p ? pack_flags(oqv, qvalid, live, winner) : (unsigned)ticks;
+    if (L.in) split_store_pack<POL>(a, rp, L, rot, qrot, qch, pack_pos(px, py, qx, qy), pack_cah(qcd, qage, hi));
+  } else {  // the state out before done / restart (multi_compute's early store, for its reason)
     const unsigned fl = (unsigned)(qvalid & 0xff) | ((unsigned)(oqv & 0xff) << 8) | ((unsigned)(live & 0xff) << 16) |
                         ((unsigned)(winner & 0xff) << 24);
-    const bool qch = __double_as_longlong(qrot) != __double_as_longlong(q_old);
+    const bool qch = (PACK && packed) || __double_as_longlong(qrot) != __double_as_longlong(q_old);
     if (L.in) split_store_state<POL>(a, r, L, px, py, rot, qx, qy, qrot, qch, qcd, qage, ticks, fl);
   }
   bool amb = false;
@@ -1254,11 +1348,15 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
     ticks = 0; live = 1; winner = 0;
   }
   const int ov = pair_swap(qvalid);  // every lane active (top level)
-  if (rs) {
+  if (PACK && to_pack) {
+    const unsigned hi = p ? pack_flags(ov, qvalid, live, winner) : (unsigned)ticks;
+    if (rs) split_store_pack<POL>(a, rp, L, rot, qrot, true, pack_pos(px, py, qx, qy), pack_cah(qcd, qage, hi));
+  } else if (rs) {
     const unsigned fl = (unsigned)(qvalid & 0xff) | ((unsigned)(ov & 0xff) << 8) | ((unsigned)(live & 0xff) << 16) |
                         ((unsigned)(winner & 0xff) << 24);
     split_store_state<POL>(a, r, L, px, py, rot, qx, qy, qrot, true, qcd, qage, ticks, fl);
   }
+  if constexpr (PACK) packed = to_pack;
   if constexpr (OBS) {
     // the future-collision flag within its margin of an edge, settled after
     // this tick's state stores (k_step_split's tail rule): by the interval
@@ -1287,7 +1385,11 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
 // "Two waves per SIMD"); `stagger` > 0 starts waves 4-7 stagger x 512
 // cycles late, so the pair alternates a tick's memory round trip with the
 // partner's arithmetic instead of both waiting at once.
-template <int POL, int BLK, bool OBS = false, int PF = 0>
+// PACK: the packed resident form between the ticks (split_tick_carry): 3 x 8
+// bytes per lane and tick each way in place of 6, so at two waves per SIMD
+// the tick is no longer bound by the fabric's bandwidth.  A compile-time
+// form: the 88-B instantiations carry no branch for it.
+template <int POL, int BLK, bool OBS = false, int PF = 0, bool PACK = false>
 __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(MultiArgs a, Cfg c, int stagger) {
   if constexpr (PF > 0) {  // the action-slab prefetch wave (k_step_multi)
     __shared__ int4 pf_scratch[64];
@@ -1310,7 +1412,8 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
   WaveCtr wc = ctr_load<BLK>(a.ctr);
   const uint64_t step0 = step_read(a.step);
   step_advance(a.step, step0, (uint64_t)a.n_ticks);
-  const __amdgpu_buffer_rsrc_t r = raw_rsrc(a.base);
+  const __amdgpu_buffer_rsrc_t r = raw_rsrc(a.base), rp = PACK ? raw_rsrc(a.pack) : r;
+  bool packed = false;  // every launch starts from (and ends in) the exchange format
   int64_t slab = a.slab0, so = a.out0;
   // the slab one tick ahead in the register pair this tick does not read,
   // two ticks per iteration (k_step_multi's action pipeline)
@@ -1323,13 +1426,15 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
   auto one_tick = [&](const float2& cur, float2& nxt) {
     SplitRaw w;
     if constexpr (PF > 0) __builtin_amdgcn_s_barrier();  // the prefetch wave (full contract at 512 lanes)
-    split_load_raw<POL>(a, r, L, w);
+    if (PACK && packed) split_load_pack<POL>(a, rp, L, w);
+    else split_load_raw<POL>(a, r, L, w);
     const int64_t ls = t + 1 < a.n_ticks ? pslab : slab;  // unconditional (see k_step_multi)
     nxt = load_action(a.actions + ls * 2 * a.n + aoff);
     __builtin_amdgcn_sched_barrier(0);
     if (tc.pend) split_carry_advance(tc);  // the last tick's rotation, while this tick's loads fly
     __builtin_amdgcn_sched_barrier(0);
-    split_tick_carry<POL, OBS>(a, c, r, L, wc, so, step0 + (uint64_t)t, w, cur, tc, t + 1 == a.n_ticks);
+    split_tick_carry<POL, OBS, PACK>(a, c, r, L, wc, so, step0 + (uint64_t)t, w, cur, tc, t + 1 == a.n_ticks, rp,
+                                     packed);
     slab = slab + 1 == a.ring ? 0 : slab + 1;
     pslab = pslab + 1 == a.ring ? 0 : pslab + 1;
     so = so + 1 == a.out_slabs ? 0 : so + 1;
@@ -1497,8 +1602,10 @@ static hipError_t launch(void (*k)(P...), dim3 grid, dim3 block, hipStream_t s, 
 
 // k_step_split_multi<POL, BLK, OBS> with its action-slab prefetch wave pf
 // ticks ahead (1, 2 or 4; 0 none; write-through port only)
-template <int POL, int BLK, bool OBS>
+// PACK (step-only, a.pack set): the packed resident form, no prefetch wave
+template <int POL, int BLK, bool OBS, bool PACK = false>
 static hipError_t launch_split_multi(int pf, dim3 g, hipStream_t hs, const MultiArgs& a, const Cfg& c, int stagger) {
+  if constexpr (PACK) return launch(k_step_split_multi<POL, BLK, false, 0, true>, g, dim3(BLK), hs, a, c, stagger);
   if constexpr (POL == 1) {
     if (pf == 1) return launch(k_step_split_multi<1, BLK, OBS, 1>, g, dim3(BLK + 64), hs, a, c, stagger);
     if (pf == 2) return launch(k_step_split_multi<1, BLK, OBS, 2>, g, dim3(BLK + 64), hs, a, c, stagger);
@@ -1681,6 +1788,15 @@ static int make_env(sk_env** out, const sk_state_view* view, int32_t n, int64_t 
   HIP_TRY(hipMemset(e->d_aux, 0, aux_bytes(n)));
   e->d_step = reinterpret_cast<uint64_t*>(e->d_aux);
   e->d_counters = reinterpret_cast<sk_counters*>(e->d_aux + 256);
+  // the packed form's scratch for the sizes that pack by default, so that no
+  // multi-tick launch has to allocate (a capturing stream cannot); a failure
+  // here leaves it to the first launch
+  if (e->multi_pack != 0 && (int64_t)n >= kSplitPackMinEnvs && (uint64_t)n * 48u <= 0xffffffffull) {
+    if (hipMalloc(&e->d_pack, (size_t)n * 48) != hipSuccess) {
+      e->d_pack = nullptr;
+      (void)hipGetLastError();
+    }
+  }
   if (e->owned) {
     k_reset<<<grid_for(n), kBlock, 0, 0>>>(e->view, n, nullptr, 0, seed, env_offset, StepRef{e->d_step, 0},
                                            e->dcfg);
@@ -2230,13 +2346,44 @@ static int step_multi(sk_env* e, const float* actions, int64_t ring_slabs, int64
   // vs 7.7); at one wave per SIMD the tick is a latency chain and the
   // pack / unpack work lengthens it (65,536: 2.51 vs 2.38; 32,768: 2.43 vs
   // 2.04; profiles/r03pk2_multi_pack_sweep.jsonl)
-  const bool want_pack = !full && (e->multi_pack > 0 || (e->multi_pack < 0 && e->n > kPackMinEnvs));
-  if (n_ticks > 1 && want_pack && (uint64_t)e->n * 48u <= 0xffffffffull) {
-    if (!e->d_pack) {
-      if (hipMalloc(&e->d_pack, (size_t)e->n * 48) != hipSuccess) return fail(SK_ENOMEM, "hipMalloc pack");
+  // In the split geometry 65,536 games already are two waves per SIMD, and
+  // there the packed form is what lifts the tick off the fabric's bandwidth
+  // (kSplitPackMinEnvs .. kSplitPackMaxEnvs).  Both kernels take the pack
+  // decision before the restart (the early store), so the packed form needs a
+  // configuration whose restart positions fit a byte.
+  const hipStream_t hs = (hipStream_t)stream;
+  const Cfg& dc = e->dcfg;
+  const bool restart_fits =
+      random_positions ? (dc.rlo >= 0 && dc.rhi <= 256)
+                       : (((unsigned)dc.f1x | (unsigned)dc.f1y | (unsigned)dc.f2x | (unsigned)dc.f2y) < 256u);
+  const bool sp_range = (int64_t)e->n >= kSplitPackMinEnvs && (int64_t)e->n <= kSplitPackMaxEnvs && restart_fits;
+  // geometry: one lane per game (k_step_multi) or two (k_step_split_multi);
+  // SK_MULTI_SPLIT = 0 / 1 forces one, else auto (kSplitMultiMaxEnvs, and the
+  // packed split kernel's range where the packed form is to be had)
+  // (the full contract always runs the split geometry: a lane per player
+  // computes that player's observation, as k_step_split does)
+  auto geometry = [&](bool pack_avail) {
+    if (full) return true;
+    if (e->multi_split >= 0) return e->multi_split != 0;
+    return (int64_t)e->n <= kSplitMultiMaxEnvs || (pack_avail && sp_range);
+  };
+  bool pack_avail = !full && n_ticks > 1 && e->multi_pack != 0 && (uint64_t)e->n * 48u <= 0xffffffffull;
+  bool split = geometry(pack_avail);
+  bool want_pack = pack_avail && restart_fits &&
+                   (e->multi_pack > 0 || (split ? sp_range : e->n > kPackMinEnvs));
+  if (want_pack && !e->d_pack) {
+    // no allocation on a capturing stream: such a launch runs the 88-B form
+    // (make_env allocates the buffer for the sizes that pack by default)
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(hs, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
+      (void)hipGetLastError();
+      want_pack = false;
+      split = geometry(false);
+    } else if (hipMalloc(&e->d_pack, (size_t)e->n * 48) != hipSuccess) {
+      return fail(SK_ENOMEM, "hipMalloc pack");
     }
-    a.pack = e->d_pack;
   }
+  if (want_pack) a.pack = e->d_pack;
   int pol = e->multi_policy;
   if (pol == 1) {  // one buffer resource over the planes: they must lie within 4 GiB of the lowest
     const char* p[6] = {(const char*)e->hview.pos, (const char*)e->hview.rot, (const char*)e->hview.qpos,
@@ -2255,19 +2402,15 @@ static int step_multi(sk_env* e, const float* actions, int64_t ring_slabs, int64
     if (ok) a.base = lo;
     else pol = 0;
   }
-  // geometry: one lane per game (k_step_multi) or two (k_step_split_multi);
-  // SK_MULTI_SPLIT = 0 / 1 forces one, else auto (kSplitMultiMaxEnvs)
-  // (the full contract always runs the split geometry: a lane per player
-  // computes that player's observation, as k_step_split does)
-  const bool split = full || (e->multi_split >= 0 ? e->multi_split != 0 : (int64_t)e->n <= kSplitMultiMaxEnvs);
-  const hipStream_t hs = (hipStream_t)stream;
   hipError_t err;
-  // the packed resident form in the lane-per-game kernel only (see
-  // k_step_split_multi)
-  const bool pk = a.pack != nullptr;
+  const bool pk = a.pack != nullptr;  // the packed resident form between the ticks
   if (split) {
     const int64_t lanes = 2 * (int64_t)e->n;
-    const bool wide = e->multi_block == 512 || (e->multi_block < 0 && lanes >= 512 * 256);
+    // 512-lane workgroups from 65,536 games for the 88-B form; the packed form
+    // stays on 64-lane ones (65,536 games 1.80 vs 1.78-1.79 us per tick, but
+    // 98,304, 384 workgroups of 512 on 256 CUs, 2.22 vs 3.31;
+    // profiles/r08_split_pack_first_sweep.jsonl)
+    const bool wide = e->multi_block == 512 || (e->multi_block < 0 && !pk && lanes >= 512 * 256);
     const dim3 g512((unsigned)((lanes + 511) / 512)), g64(step_grid(lanes));
     // the action-slab prefetch wave: SK_MULTI_PREFETCH, else, at 400 ticks
     // per launch: the full contract 4 ticks ahead on 512-lane workgroups
@@ -2296,6 +2439,11 @@ static int step_multi(sk_env* e, const float* actions, int64_t ring_slabs, int64
                              : launch_split_multi<0, 512, true>(pf, g512, hs, a, e->dcfg, sg))
                  : (pol == 1 ? launch_split_multi<1, kStepBlock, true>(pf, g64, hs, a, e->dcfg, sg)
                              : launch_split_multi<0, kStepBlock, true>(pf, g64, hs, a, e->dcfg, sg));
+    else if (pk)  // the packed form: no prefetch wave
+      err = wide ? (pol == 1 ? launch_split_multi<1, 512, false, true>(0, g512, hs, a, e->dcfg, sg)
+                             : launch_split_multi<0, 512, false, true>(0, g512, hs, a, e->dcfg, sg))
+                 : (pol == 1 ? launch_split_multi<1, kStepBlock, false, true>(0, g64, hs, a, e->dcfg, sg)
+                             : launch_split_multi<0, kStepBlock, false, true>(0, g64, hs, a, e->dcfg, sg));
     else
       err = wide ? (pol == 1 ? launch_split_multi<1, 512, false>(pf, g512, hs, a, e->dcfg, sg)
                              : launch_split_multi<0, 512, false>(pf, g512, hs, a, e->dcfg, sg))
