@@ -579,7 +579,11 @@ __device__ __forceinline__ void tick_env_fast(const Cfg& c, Env& e, float a0_mov
 // So tick t - 1's final rotations are the only new arguments: their exact
 // sincos (sincos_bf, the library past its range — the same values tick_env_m
 // computes) is evaluated at the top of tick t, after tick t's loads are
-// issued, in the shadow of the memory round trip.  Each value is KEYED by the
+// issued, in the shadow of the memory round trip (free only where a SIMD
+// holds one wave: with two or three co-resident waves whatever a wave issues
+// adds to the tick, which is why the step-only split tick carries the fp32
+// sincos_fast and integer steps instead, split_tick_carry's FAST form in
+// sk_engine.hip).  Each value is KEYED by the
 // rotation it is the sincos of and used only where the key equals the
 // rotation just loaded (bitwise); any lane that misses (tick 0 of a launch)
 // sends its wave through the full evaluation.  The state still makes its

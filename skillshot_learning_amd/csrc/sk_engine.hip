@@ -20,7 +20,8 @@
 //                         optionally an action-slab prefetch wave; step-only
 //                         also with the packed 48-B form between ticks (8 B
 //                         per player and plane), the default from 40,960 to
-//                         98,304 games
+//                         98,304 games, there in long launches on fp32 trig
+//                         with the wave's exact fallback (FAST)
 //     both run the carried-sincos tick: tick_env_carry (sk_device.hpp) and
 //     split_tick_carry (below)
 //   k_rollout_random      n ticks of the random policy in one launch, state
@@ -80,6 +81,10 @@ struct sk_env {
   // k_step_split_multi): -1 auto (above one wave per SIMD), 1 / 0 force
   // (SK_MULTI_PACK)
   int multi_pack;
+  // the step-only k_step_split_multi on fp32 trig with the exact fallback
+  // (split_tick_carry's FAST form): -1 auto (the packed form's sizes in
+  // launches from kFastSplitMinTicks ticks), 1 / 0 force (SK_MULTI_FAST)
+  int multi_fast;
   char* d_pack;  // its scratch (48 B x n): make_env for the sizes that pack by default, else the first packed launch
   // device = -1: the CPU backend (sk_host.cpp) owns the games; every entry
   // point below forwards to it and takes host pointers
@@ -131,6 +136,18 @@ static constexpr int64_t kSplitMultiMaxEnvs = 32768;  // k_step: restart draw un
 // packed form (profiles/r08_split_pack_boundary.jsonl)
 static constexpr int64_t kSplitPackMinEnvs = 40960;
 static constexpr int64_t kSplitPackMaxEnvs = 98304;
+// k_step_split_multi's fp32-trig tick (FAST) where several waves share a SIMD
+// and the launch is long: 267 against 321 VALU per wave and tick.  Write-
+// through port, us per tick, fast against the fp64 carry at 400 / 100 / 20
+// ticks per launch: 40,960 games 1.64-1.65 vs 1.69-1.70 / 1.68-1.70 vs 1.72 /
+// 1.92 vs 1.87-1.88; 65,536 1.71 vs 1.75-1.76 / 1.75-1.76 vs 1.78-1.79 /
+// 2.09 vs 1.96-1.97; 98,304 2.04-2.06 vs 2.17-2.22 / 2.09-2.11 vs 2.21-2.22 /
+// 2.43-2.44 either way.  One wave per SIMD loses at every launch length
+// (8,192: 1.27 vs 1.19 / 1.31 vs 1.21 / 1.48 vs 1.33; 32,768: 1.40 vs 1.35 /
+// 1.45 vs 1.40 / 1.73 vs 1.53): there the tick is a latency chain and the
+// fp64 carry runs under the loads for nothing
+// (profiles/r09_split_fast_sweep.jsonl)
+static constexpr int kFastSplitMinTicks = 100;
 // SK_CTR_STRIDE slots per wave of the widest step grid (k_step_split: two
 // lanes per game), at least SK_COUNTER_SLOTS
 static inline int64_t counter_slots(int64_t n) {
@@ -1059,8 +1076,8 @@ struct SplitLane {
 
 // ---- the split tick (split_tick_carry): k_step_multi's carried-sincos tick
 // in the split geometry.  The lane's player's rotation sincos is
-// carried from the previous tick (evaluated at the top of the tick under its
-// loads, keyed by the rotation's bits), a projectile in flight keeps its
+// carried from the previous tick (evaluated at the top of the tick after its
+// loads are issued, keyed by the rotation's bits), a projectile in flight keeps its
 // carried sincos, a fired one gets its step by fp32 angle addition with the
 // wave's exact fallback (tick_env_carry, sk_device.hpp); the commits are
 // selects; the action slab is loaded one tick ahead; the state halves are
@@ -1086,6 +1103,35 @@ __device__ __forceinline__ void split_carry_advance(SplitCarry& t) {
   t.have = true;
   t.pend = false;
 }
+// FAST (step-only): the carry in fp32.  The tick never stores a sine, only
+// int(round(p - d)), so what is carried is sincos_fast of the rotation (the
+// move's deltas and a fired projectile's angle addition start from it) and,
+// for the projectile in flight, its integer step: round_safe holds for every
+// integer p, so the step rintf(ex), rintf(ey) taken at the launch is the
+// flight's.  `qex`: that step could not be decided in fp32 (a delta within
+// its bound of a half-integer, or a rotation outside the fast range); such a
+// lane sends its wave through the exact evaluation every tick of the flight.
+struct SplitCarryF {
+  double kr, kq;      // keys: m = sincos_fast(kr), (dx, dy) = the step of a projectile with rotation kq
+  sktrig::SinCosF m;
+  int dx, dy;
+  double pr;          // the last tick's final rotation (evaluated at the next tick's top)
+  bool mok, qex, have, pend;
+};
+__device__ __forceinline__ void split_carry_advance(SplitCarryF& t) {
+  t.m = sktrig::sincos_fast(t.pr, &t.mok);
+  t.kr = t.pr;
+  t.have = true;
+  t.pend = false;
+}
+template <bool FAST>
+struct SplitCarrySel {
+  using type = SplitCarry;
+};
+template <>
+struct SplitCarrySel<true> {
+  using type = SplitCarryF;
+};
 struct SplitRaw {
   skb2i rot, qrot, pp, ca, qq, mi;
 };
@@ -1138,7 +1184,9 @@ __device__ __forceinline__ void split_load_pack(const MultiArgs& a, __amdgpu_buf
     w.qrot = __builtin_amdgcn_raw_buffer_load_b64(rp, o + plane, 0, 16);
     w.pp = __builtin_amdgcn_raw_buffer_load_b64(rp, o + 2u * plane, 0, 16);
   }
-  w.ca = w.qq = w.mi = (skb2i){0, 0};
+  // w.ca / qq / mi stay unwritten: a packed tick never reads them, and they
+  // are the 88-B path's load destinations (writing them here made the wave
+  // wait for its earlier stores before the work under the round trip began)
   __builtin_amdgcn_sched_barrier(0);
 }
 template <int POL>
@@ -1170,12 +1218,24 @@ __device__ __forceinline__ void split_store_pack(const MultiArgs& a, __amdgpu_bu
 // fits: the host checks the configuration's restart positions); the
 // launch's first tick loads and its last stores the exchange format, and a
 // tick that follows a packed one stores the qrot plane regardless.
-template <int POL, bool OBS, bool PACK = false>
+//
+// FAST (step-only): fp32 trig off the carry with the wave's exact fallback
+// (SplitCarryF; tick_env_fast's error budget).  The move's deltas come from
+// the carried sincos_fast, a fired projectile's step from its angle addition,
+// the step of one in flight is carried as two integers.  A wave with a lane
+// whose move or fired step is within its bound of a half-integer, whose
+// projectile in flight is flagged exact-only, whose rotation is outside the
+// fast range or whose action is not finite evaluates sincos_bf (the library
+// past its range) and takes the fp64 expressions of the other form: the same
+// result bit for bit, about one wave-tick in a few hundred.
+template <int POL, bool OBS, bool PACK = false, bool FAST = false>
 __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& c, __amdgpu_buffer_rsrc_t r,
                                                  SplitLane& L, WaveCtr& wc, int64_t so, uint64_t step,
-                                                 const SplitRaw& w, float2 act, SplitCarry& tc, bool last,
+                                                 const SplitRaw& w, float2 act,
+                                                 typename SplitCarrySel<FAST>::type& tc, bool last,
                                                  __amdgpu_buffer_rsrc_t rp, bool& packed) {
   static_assert(!(OBS && PACK), "the full contract never packs");
+  static_assert(!(OBS && FAST), "the observation needs the exact sincos");
   using sktrig::round_safe;
   const int p = L.p;
   double rot = __builtin_bit_cast(double, w.rot), qrot = __builtin_bit_cast(double, w.qrot);
@@ -1197,12 +1257,22 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
   const bool f = qcd <= 0;  // fires this tick (Player.py:80)
   const bool miss = !tc.have || !same_bits(rot, tc.kr) || (qvalid && !f && !same_bits(qrot, tc.kq));
   if (__ballot(L.in && miss) != 0) {  // the launch's first tick
-    bool k0, k1;
-    tc.m = sktrig::sincos_bf(rot, &k0);
-    tc.tq = sktrig::sincos_bf(qrot, &k1);
-    if (!(k0 & k1)) {
-      if (!k0) tc.m = sincos_lib(rot);
-      if (!k1) tc.tq = sincos_lib(qrot);
+    if constexpr (FAST) {
+      bool kq;
+      tc.m = sktrig::sincos_fast(rot, &tc.mok);
+      const sktrig::SinCosF q = sktrig::sincos_fast(qrot, &kq);
+      const sktrig::FastDelta d = sktrig::fast_step_delta(q, kq, (float)c.qspeed);
+      tc.qex = !d.safe;
+      tc.dx = (int)rintf(d.x);
+      tc.dy = (int)rintf(d.y);
+    } else {
+      bool k0, k1;
+      tc.m = sktrig::sincos_bf(rot, &k0);
+      tc.tq = sktrig::sincos_bf(qrot, &k1);
+      if (!(k0 & k1)) {
+        if (!k0) tc.m = sincos_lib(rot);
+        if (!k1) tc.tq = sincos_lib(qrot);
+      }
     }
     tc.kr = rot;
     tc.kq = qrot;
@@ -1211,11 +1281,29 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
   const float l = clamp_action_f(act.y);
   const double rn = rot + (double)l * c.look;  // == move_look_s
   const float lk = (float)c.look, qsf = (float)c.qspeed, eq = 2e-6f * qsf;
-  const sktrig::SinCosF u = sktrig::sincos_add(sktrig::SinCosF{(float)tc.m.s, (float)tc.m.c}, l * lk);
+  sktrig::SinCosF mf;
+  if constexpr (FAST) mf = tc.m;
+  else mf = sktrig::SinCosF{(float)tc.m.s, (float)tc.m.c};
+  const sktrig::SinCosF u = sktrig::sincos_add(mf, l * lk);
   const float ex = u.s * qsf, ey = u.c * qsf;
-  const bool un = f && !((int)(fabs(rot) < 1647099.3291652855) & (int)round_safe(ex, eq) & (int)round_safe(ey, eq));
-  sktrig::SinCos tt = tc.tq;  // in flight: the carried exact value
-  bool fast = f;
+  bool un, unq = false;
+  float mdx = 0.0f, mdy = 0.0f;  // FAST: the move's deltas
+  sktrig::SinCos tt{0.0, 1.0};   // the projectile's exact sincos (FAST: on the exact path only)
+  sktrig::SinCos tm{0.0, 1.0};   // the move's
+  if constexpr (FAST) {
+    const sktrig::FastDelta dm = sktrig::fast_move_delta(tc.m, tc.mok, (float)c.pspeed, clamp_action_f(act.x));
+    mdx = dm.x;
+    mdy = dm.y;
+    unq = f && !sktrig::fast_step_delta(u, tc.mok, qsf).safe;  // its deltas are ex, ey
+    un = !dm.safe || unq || (qvalid && !f && tc.qex);
+  } else {
+    un = f && !((int)(fabs(rot) < 1647099.3291652855) & (int)round_safe(ex, eq) & (int)round_safe(ey, eq));
+    tt = tc.tq;  // in flight: the carried exact value
+    tm = tc.m;
+  }
+  bool fast = f;   // the fired step from fp32 (the other form)
+  bool exact = false;  // FAST, wave-uniform: this tick takes the fp64 expressions' results
+  int epx = 0, epy = 0, enx = 0, eny = 0;  // ... the post-move position and the projectile's candidate
   sktrig::SinCos xn{0.0, 1.0};    // OBS: sincos(rn), exact
   sktrig::SinCosF pr{0.0f, 1.0f};  // OBS: sincos(rn) in fp32 (obs12_sc)
   if constexpr (OBS) {
@@ -1232,25 +1320,56 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
     }
   }
   if (__builtin_expect(__ballot(L.in && un) != 0, 0)) {  // the exact sincos of the fired projectiles
-    sktrig::SinCos x = xn;
-    if constexpr (!OBS) {
-      bool k;
-      x = sktrig::sincos_bf(rn, &k);
-      if (!k) x = sincos_lib(rn);
+    if constexpr (FAST) {  // ... and of the move and the projectile in flight
+      const double qa = f ? rn : qrot;
+      bool k0, k1;
+      tm = sktrig::sincos_bf(rot, &k0);
+      tt = sktrig::sincos_bf(qa, &k1);
+      if (!(k0 & k1)) {
+        if (!k0) tm = sincos_lib(rot);
+        if (!k1) tt = sincos_lib(qa);
+      }
+      // today's fp64 expressions of the other form, for the whole wave (a
+      // lane the fast path could decide gets the same integers): the move,
+      // then the projectile from where shoot leaves it
+      const double speed = clamp_action((double)act.x), psp = (double)c.pspeed, qsp = (double)c.qspeed;
+      const double nxf = __builtin_rint((double)px - (tm.s * psp) * speed);
+      const double nyf = __builtin_rint((double)py - (tm.c * psp) * speed);
+      const bool ok = (nxf >= 0.0) & (nxf + (double)c.psize <= (double)c.W) & (nyf >= 0.0) &
+                      (nyf + (double)c.psize <= (double)c.H);
+      epx = ok ? (int)(ok ? nxf : 0.0) : px;
+      epy = ok ? (int)(ok ? nyf : 0.0) : py;
+      enx = (int)__builtin_rint((double)(f ? epx : qx) - tt.s * qsp);
+      eny = (int)__builtin_rint((double)(f ? epy : qy) - tt.c * qsp);
+      exact = true;
+    } else {
+      sktrig::SinCos x = xn;
+      if constexpr (!OBS) {
+        bool k;
+        x = sktrig::sincos_bf(rn, &k);
+        if (!k) x = sincos_lib(rn);
+      }
+      if (f) tt = x;
+      fast = false;
     }
-    if (f) tt = x;
-    fast = false;
   }
-  const sktrig::SinCos tq_obs = f ? xn : tc.tq;  // OBS: the projectile's sincos after shoot
+  sktrig::SinCos tq_obs{0.0, 1.0};  // OBS: the projectile's sincos after shoot
+  if constexpr (OBS) tq_obs = f ? xn : tc.tq;
   // do_actions(p + 1, ...)  SkillshotLearner.py:206-213 (Player.py:57-68, :33-39, :78-89)
-  {
+  if constexpr (!FAST) {
     const double speed = clamp_action((double)act.x), psp = (double)c.pspeed;
-    const double nxf = __builtin_rint((double)px - (tc.m.s * psp) * speed);
-    const double nyf = __builtin_rint((double)py - (tc.m.c * psp) * speed);
+    const double nxf = __builtin_rint((double)px - (tm.s * psp) * speed);
+    const double nyf = __builtin_rint((double)py - (tm.c * psp) * speed);
     const bool ok = (nxf >= 0.0) & (nxf + (double)c.psize <= (double)c.W) & (nyf >= 0.0) &
                     (nyf + (double)c.psize <= (double)c.H);
     px = ok ? (int)(ok ? nxf : 0.0) : px;
     py = ok ? (int)(ok ? nyf : 0.0) : py;
+  } else {  // round_safe: rint(p - d) == p - rintf(d); player_pos_valid's bounds, safe against wrap
+    // (selects on the wave-uniform `exact`, no branch: the tick's chain stays one block)
+    const int nx = px - (int)rintf(mdx), ny = py - (int)rintf(mdy);
+    const bool ok = (nx >= 0) & (nx <= c.W - c.psize) & (ny >= 0) & (ny <= c.H - c.psize);
+    px = exact ? epx : (ok ? nx : px);
+    py = exact ? epy : (ok ? ny : py);
   }
   rot = rn;
   qx = f ? px : qx;
@@ -1264,9 +1383,23 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
   ticks += lv;
   {
     const double qsp = (double)c.qspeed;
-    const int nxF = qx - (int)rintf(ex), nyF = qy - (int)rintf(ey);
-    const int nxE = (int)__builtin_rint((double)qx - tt.s * qsp), nyE = (int)__builtin_rint((double)qy - tt.c * qsp);
-    const int nx = fast ? nxF : nxE, ny = fast ? nyF : nyE;
+    int nx, ny;
+    if constexpr (FAST) {
+      // the step of this tick: a fired projectile's from the angle addition,
+      // else the carried one; either way the flight's from here on
+      const int sdx = f ? (int)rintf(ex) : tc.dx, sdy = f ? (int)rintf(ey) : tc.dy;
+      tc.dx = sdx;
+      tc.dy = sdy;
+      tc.qex = f ? unq : tc.qex;
+      tc.kq = f ? rn : tc.kq;
+      nx = exact ? enx : qx - sdx;
+      ny = exact ? eny : qy - sdy;
+    } else {
+      const int nxF = qx - (int)rintf(ex), nyF = qy - (int)rintf(ey);
+      const int nxE = (int)__builtin_rint((double)qx - tt.s * qsp), nyE = (int)__builtin_rint((double)qy - tt.c * qsp);
+      nx = fast ? nxF : nxE;
+      ny = fast ? nyF : nyE;
+    }
     const bool ok = (nx + c.qsize <= c.W) & (nx >= 0) & (ny + c.qsize <= c.H) & (ny >= 0);
     const bool upd = lv && qvalid;
     qx = (upd && ok) ? nx : qx;
@@ -1375,7 +1508,7 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
     tc.have = true;
   } else if (!last) {  // the tick's final rotation: the next tick's carried sincos
     tc.pr = rot;
-    tc.qs = same_bits(qrot, rot);
+    if constexpr (!FAST) tc.qs = same_bits(qrot, rot);
     tc.pend = true;
   }
 }
@@ -1389,7 +1522,9 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
 // bytes per lane and tick each way in place of 6, so at two waves per SIMD
 // the tick is no longer bound by the fabric's bandwidth.  A compile-time
 // form: the 88-B instantiations carry no branch for it.
-template <int POL, int BLK, bool OBS = false, int PF = 0, bool PACK = false>
+// FAST: the step-only tick on fp32 trig with the exact fallback
+// (split_tick_carry), also a compile-time form.
+template <int POL, int BLK, bool OBS = false, int PF = 0, bool PACK = false, bool FAST = false>
 __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(MultiArgs a, Cfg c, int stagger) {
   if constexpr (PF > 0) {  // the action-slab prefetch wave (k_step_multi)
     __shared__ int4 pf_scratch[64];
@@ -1420,7 +1555,7 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
   const int64_t aoff = (int64_t)L.p * a.n + L.ic;
   float2 pa0 = load_action(a.actions + slab * 2 * a.n + aoff), pa1;
   int64_t pslab = slab + 1 == a.ring ? 0 : slab + 1;
-  SplitCarry tc;
+  typename SplitCarrySel<FAST>::type tc;
   tc.have = tc.pend = false;
   int t = 0;
   auto one_tick = [&](const float2& cur, float2& nxt) {
@@ -1431,10 +1566,13 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
     const int64_t ls = t + 1 < a.n_ticks ? pslab : slab;  // unconditional (see k_step_multi)
     nxt = load_action(a.actions + ls * 2 * a.n + aoff);
     __builtin_amdgcn_sched_barrier(0);
-    if (tc.pend) split_carry_advance(tc);  // the last tick's rotation, while this tick's loads fly
+    // the last tick's rotation, while this tick's loads fly: hidden at one
+    // wave per SIMD, paid in issue slots with co-resident waves (FAST: 32
+    // VALU, 9 of them fp64, against 89 and 50)
+    if (tc.pend) split_carry_advance(tc);
     __builtin_amdgcn_sched_barrier(0);
-    split_tick_carry<POL, OBS, PACK>(a, c, r, L, wc, so, step0 + (uint64_t)t, w, cur, tc, t + 1 == a.n_ticks, rp,
-                                     packed);
+    split_tick_carry<POL, OBS, PACK, FAST>(a, c, r, L, wc, so, step0 + (uint64_t)t, w, cur, tc, t + 1 == a.n_ticks,
+                                           rp, packed);
     slab = slab + 1 == a.ring ? 0 : slab + 1;
     pslab = pslab + 1 == a.ring ? 0 : pslab + 1;
     so = so + 1 == a.out_slabs ? 0 : so + 1;
@@ -1603,15 +1741,26 @@ static hipError_t launch(void (*k)(P...), dim3 grid, dim3 block, hipStream_t s, 
 // k_step_split_multi<POL, BLK, OBS> with its action-slab prefetch wave pf
 // ticks ahead (1, 2 or 4; 0 none; write-through port only)
 // PACK (step-only, a.pack set): the packed resident form, no prefetch wave
-template <int POL, int BLK, bool OBS, bool PACK = false>
+// FAST (step-only): the fp32-trig tick
+template <int POL, int BLK, bool OBS, bool PACK = false, bool FAST = false>
 static hipError_t launch_split_multi(int pf, dim3 g, hipStream_t hs, const MultiArgs& a, const Cfg& c, int stagger) {
-  if constexpr (PACK) return launch(k_step_split_multi<POL, BLK, false, 0, true>, g, dim3(BLK), hs, a, c, stagger);
+  if constexpr (PACK)
+    return launch(k_step_split_multi<POL, BLK, false, 0, true, FAST>, g, dim3(BLK), hs, a, c, stagger);
   if constexpr (POL == 1) {
-    if (pf == 1) return launch(k_step_split_multi<1, BLK, OBS, 1>, g, dim3(BLK + 64), hs, a, c, stagger);
-    if (pf == 2) return launch(k_step_split_multi<1, BLK, OBS, 2>, g, dim3(BLK + 64), hs, a, c, stagger);
-    if (pf > 2) return launch(k_step_split_multi<1, BLK, OBS, 4>, g, dim3(BLK + 64), hs, a, c, stagger);
+    if (pf == 1) return launch(k_step_split_multi<1, BLK, OBS, 1, false, FAST>, g, dim3(BLK + 64), hs, a, c, stagger);
+    if (pf == 2) return launch(k_step_split_multi<1, BLK, OBS, 2, false, FAST>, g, dim3(BLK + 64), hs, a, c, stagger);
+    if (pf > 2) return launch(k_step_split_multi<1, BLK, OBS, 4, false, FAST>, g, dim3(BLK + 64), hs, a, c, stagger);
   }
-  return launch(k_step_split_multi<POL, BLK, OBS>, g, dim3(BLK), hs, a, c, stagger);
+  return launch(k_step_split_multi<POL, BLK, OBS, 0, false, FAST>, g, dim3(BLK), hs, a, c, stagger);
+}
+// ... by workgroup width and state port
+template <bool OBS, bool PACK, bool FAST>
+static hipError_t launch_split_geom(bool wide, int pol, int pf, dim3 g512, dim3 g64, hipStream_t hs,
+                                    const MultiArgs& a, const Cfg& c, int sg) {
+  return wide ? (pol == 1 ? launch_split_multi<1, 512, OBS, PACK, FAST>(pf, g512, hs, a, c, sg)
+                          : launch_split_multi<0, 512, OBS, PACK, FAST>(pf, g512, hs, a, c, sg))
+              : (pol == 1 ? launch_split_multi<1, kStepBlock, OBS, PACK, FAST>(pf, g64, hs, a, c, sg)
+                          : launch_split_multi<0, kStepBlock, OBS, PACK, FAST>(pf, g64, hs, a, c, sg));
 }
 
 // k_step_multi<POL, PACK, BLK> with its feed wave pf ticks ahead (1, 2 or 4;
@@ -1738,6 +1887,8 @@ static int make_env(sk_env** out, const sk_state_view* view, int32_t n, int64_t 
   if (const char* mp = std::getenv("SK_MULTI_PREFETCH")) e->multi_prefetch = std::atoi(mp);
   e->multi_pack = -1;
   if (const char* mk = std::getenv("SK_MULTI_PACK")) e->multi_pack = std::atoi(mk);
+  e->multi_fast = -1;
+  if (const char* mf = std::getenv("SK_MULTI_FAST")) e->multi_fast = std::atoi(mf);
   e->d_pack = nullptr;
   if (view) {
     if (view->n_envs != n || !view->pos || !view->rot || !view->qpos || !view->qrot || !view->qcdage ||
@@ -2434,21 +2585,20 @@ static int step_multi(sk_env* e, const float* actions, int64_t ring_slabs, int64
                    : (e->n > 8192 && !wide) ? 2
                                               : 0;
     const int sg = wide ? e->multi_stagger : 0;
+    // the fp32-trig tick (step-only): SK_MULTI_FAST = 0 / 1 forces, else auto:
+    // the packed form's sizes (kSplitPackMinEnvs) in launches from
+    // kFastSplitMinTicks ticks
+    const bool fastf = !full && (e->multi_fast >= 0 ? e->multi_fast != 0
+                                                    : (pk && (int64_t)e->n >= kSplitPackMinEnvs &&
+                                                       n_ticks >= kFastSplitMinTicks));
     if (full)
-      err = wide ? (pol == 1 ? launch_split_multi<1, 512, true>(pf, g512, hs, a, e->dcfg, sg)
-                             : launch_split_multi<0, 512, true>(pf, g512, hs, a, e->dcfg, sg))
-                 : (pol == 1 ? launch_split_multi<1, kStepBlock, true>(pf, g64, hs, a, e->dcfg, sg)
-                             : launch_split_multi<0, kStepBlock, true>(pf, g64, hs, a, e->dcfg, sg));
+      err = launch_split_geom<true, false, false>(wide, pol, pf, g512, g64, hs, a, e->dcfg, sg);
     else if (pk)  // the packed form: no prefetch wave
-      err = wide ? (pol == 1 ? launch_split_multi<1, 512, false, true>(0, g512, hs, a, e->dcfg, sg)
-                             : launch_split_multi<0, 512, false, true>(0, g512, hs, a, e->dcfg, sg))
-                 : (pol == 1 ? launch_split_multi<1, kStepBlock, false, true>(0, g64, hs, a, e->dcfg, sg)
-                             : launch_split_multi<0, kStepBlock, false, true>(0, g64, hs, a, e->dcfg, sg));
+      err = fastf ? launch_split_geom<false, true, true>(wide, pol, 0, g512, g64, hs, a, e->dcfg, sg)
+                  : launch_split_geom<false, true, false>(wide, pol, 0, g512, g64, hs, a, e->dcfg, sg);
     else
-      err = wide ? (pol == 1 ? launch_split_multi<1, 512, false>(pf, g512, hs, a, e->dcfg, sg)
-                             : launch_split_multi<0, 512, false>(pf, g512, hs, a, e->dcfg, sg))
-                 : (pol == 1 ? launch_split_multi<1, kStepBlock, false>(pf, g64, hs, a, e->dcfg, sg)
-                             : launch_split_multi<0, kStepBlock, false>(pf, g64, hs, a, e->dcfg, sg));
+      err = fastf ? launch_split_geom<false, false, true>(wide, pol, pf, g512, g64, hs, a, e->dcfg, sg)
+                  : launch_split_geom<false, false, false>(wide, pol, pf, g512, g64, hs, a, e->dcfg, sg);
   } else {
     // the restart draw under the loads (k_step's early draw): off in round 3
     // (65,536 games 2.73 vs 2.81 us per tick at 20 ticks per launch;

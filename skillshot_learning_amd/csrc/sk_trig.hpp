@@ -174,4 +174,36 @@ SKT_HD bool round_safe(float d, float eps) {
   return fabsf(t - 0.5f) > eps;
 }
 
+// The fast decisions of a tick (tick_env_fast's error budget, sk_device.hpp),
+// shared by the kernels and tests/fast_step_check.cpp.  `safe`: both fp32
+// deltas decide int(round(p - d)) == p - (int)rintf(d) for every integer p.
+struct FastDelta {
+  float x, y;
+  bool safe;
+};
+
+// a player's move: d = (sin/cos * speed) * a, a the clamped move action;
+// m = sincos_fast of the rotation and its ok.  Bound 4.2e-7 * speed,
+// threshold 1e-6 * speed.  A NaN action fails round_safe.
+SKT_HD FastDelta fast_move_delta(SinCosF m, bool ok, float speed, float a) {
+  FastDelta o;
+  const float eps = 1e-6f * speed;
+  o.x = (m.s * speed) * a;
+  o.y = (m.c * speed) * a;
+  o.safe = (int)ok & (int)round_safe(o.x, eps) & (int)round_safe(o.y, eps);
+  return o;
+}
+
+// a projectile's step: d = sin/cos * speed, q = sincos_fast of its rotation
+// or sincos_add of the firing player's.  Bound 6.6e-7 * speed, threshold
+// 2e-6 * speed.
+SKT_HD FastDelta fast_step_delta(SinCosF q, bool ok, float speed) {
+  FastDelta o;
+  const float eps = 2e-6f * speed;
+  o.x = q.s * speed;
+  o.y = q.c * speed;
+  o.safe = (int)ok & (int)round_safe(o.x, eps) & (int)round_safe(o.y, eps);
+  return o;
+}
+
 }  // namespace sktrig

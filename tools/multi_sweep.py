@@ -18,7 +18,7 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 
 
-def multi_rate(n, T, pol, split=-1, stagger=0, block=-1, fast=0, early=-1, K=2000, ring=400, seed=0, prefetch=0,
+def multi_rate(n, T, pol, split=-1, stagger=0, block=-1, fast=-1, early=-1, K=2000, ring=400, seed=0, prefetch=0,
                pack=-1):
     os.environ["SK_MULTI_PREFETCH"] = str(prefetch)
     os.environ["SK_MULTI_PACK"] = str(pack)
@@ -78,7 +78,7 @@ def main():
     p.add_argument("--splits", default="-1")
     p.add_argument("--staggers", default="0")
     p.add_argument("--blocks", default="-1")
-    p.add_argument("--fasts", default="0")
+    p.add_argument("--fasts", default="-1", help="SK_MULTI_FAST values (-1 auto, 0 fp64 carry, 1 fp32-trig split tick)")
     p.add_argument("--earlys", default="-1")
     p.add_argument("--rings", default="400", help="action slabs in the ring (400: larger than the Infinity Cache)")
     p.add_argument("--prefetches", default="0", help="SK_MULTI_PREFETCH values (k_step_multi's prefetch wave)")
