@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define SK_ABI_VERSION 12
+#define SK_ABI_VERSION 13
 
 enum {
   SK_OK = 0,
@@ -266,6 +266,37 @@ int sk_env_act_episode(sk_env* env, const float* actor_flat, const void* actor_p
                        float* rewards, int32_t* lengths, int32_t n_ticks, float noise_sd, float action_sd,
                        uint64_t noise_seed, uint64_t* call_counter, int32_t reward_kind, int32_t tick_limit,
                        void* stream);
+
+/* Head-to-head evaluation in ONE launch (ABI 13; the loop of
+ * SkillshotLearner.py:302-318 with two policies): every game plays from the
+ * current state while game_live and ticks < tick_limit, and the two seats
+ * act from DIFFERENT nets — seat 1 (player id 1) from actor1, seat 2 (player
+ * id 2) from actor2, both fp32 actors with their split packs
+ * (sk_actor_split_pack_f32), without parameter or action noise: the match is
+ * deterministic and neither actor's noise call number is read or written.  A
+ * game that has ended is neither stepped nor written again, so the state
+ * planes hold every game's final state; winner_id there is the id of the
+ * player who was HIT (SkillshotGame.py:76-78), i.e. the loser's seat.
+ * obs2 float[2][2][N][12] (16-byte aligned) is a ping-pong pair of
+ * observation buffers: half 0 holds the observation of the current state
+ * (sk_env_observe) on entry, tick t reads half t & 1 and writes half
+ * (t + 1) & 1.  A game that played L ticks of this call has its newest
+ * observation in half L & 1.  No trajectory is recorded.
+ * returns float[2][N] (nullable) is in/out: the call adds, in fp32 and in
+ * tick order, each player's rewards of the ticks its game played (reward_kind
+ * as sk_env_step's) onto the values found there — zero it before a match's
+ * first call.  lengths int32[N] = the ticks each game played in this call.
+ * last_half (nullable, device int32) receives n_ticks & 1, the half a game
+ * still live after n_ticks ticks acts from next.  Such a game continues in
+ * the next call: the caller passes its newest observation as half 0 again
+ * (nothing to do after an even n_ticks; after an odd one copy those games'
+ * rows of half 1 to half 0).  Any N >= 1.  The step counter advances by max_i lengths[i], the
+ * iterations of the per-tick loop this replaces (sk_env_act_episode's second
+ * one-workgroup launch); no episode counters.  Stream-ordered and
+ * graph-capturable.  GPU backend only. */
+int sk_env_act_match(sk_env* env, const float* actor1_flat, const void* actor1_pack, const float* actor2_flat,
+                     const void* actor2_pack, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
+                     int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, void* stream);
 
 /* sk_env_act_step prepared, not launched (ABI 8): the same arguments
  * (N % 4 == 0, ring given or not) into *job, and the env advances its step

@@ -2407,6 +2407,28 @@ int sk_env_act_episode(sk_env* e, const float* actor_flat, const void* actor_pac
   return SK_OK;
 }
 
+int sk_env_act_match(sk_env* e, const float* actor1_flat, const void* actor1_pack, const float* actor2_flat,
+                     const void* actor2_pack, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
+                     int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, void* stream) {
+  SK_CHECK_ENV(e);
+  if (!actor1_flat || !actor2_flat || !actor1_pack || !actor2_pack || !obs2 || !lengths || n_ticks <= 0)
+    return fail(SK_EINVAL, "an actor's flat / pack, obs2 or lengths is NULL, or n_ticks <= 0");
+  if (e->host) return fail(SK_EINVAL, "sk_env_act_match runs on the GPU backend");
+  if ((((uintptr_t)actor1_pack) | ((uintptr_t)actor2_pack)) & 15)
+    return fail(SK_EINVAL, "actor1_pack / actor2_pack must be 16-byte aligned");
+  if ((((uintptr_t)lengths) | ((uintptr_t)returns) | ((uintptr_t)last_half)) & 3)
+    return fail(SK_EINVAL, "lengths / returns / last_half must be 4-byte aligned");
+  StepArgs a;  // (checks obs2's 16-byte alignment and reward_kind; both halves are 96 N bytes apart)
+  int rc = act_step_args(e, obs2, nullptr, obs2, returns, reward_kind, nullptr, nullptr, tick_limit, 0, 0, nullptr,
+                         nullptr, 0, nullptr, nullptr, nullptr, a);
+  if (rc != SK_OK) return rc;
+  rc = sk_launch_act_match32(actor1_flat, actor1_pack, actor2_flat, actor2_pack, a, e->dcfg, obs2, returns, lengths,
+                             last_half, n_ticks, (hipStream_t)stream);
+  if (rc != SK_OK) return fail(rc, "k_act_match32 launch failed");
+  e->parity ^= 1;
+  return SK_OK;
+}
+
 static_assert(sizeof(ActStepJob) <= sizeof(sk_step_job), "sk_step_job too small for ActStepJob");
 
 int sk_env_act_step_job(sk_env* e, const float* actor_flat, const void* actor_pack, const float* acting_obs,

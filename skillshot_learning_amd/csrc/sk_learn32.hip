@@ -1576,14 +1576,25 @@ __device__ __forceinline__ void noisy4(uint64_t seed, uint64_t call, uint32_t r,
 // row (the first row of an aligned 4-row group), so with N % 4 == 0 both maps
 // draw the same noise for the same row.
 struct RowsContig {
+  static constexpr bool kStore = true;  // the tile writes its actions to `out` (compile time)
   int64_t row0, rows;
   __device__ int64_t operator()(int i) const { return row0 + i; }
   __device__ bool valid(int i) const { return row0 + i < rows; }
 };
 struct RowsPlayers {
+  static constexpr bool kStore = true;
   int64_t g0, n;
   __device__ int64_t operator()(int i) const { return i < 16 ? g0 + i : n + g0 + (i - 16); }
   __device__ bool valid(int i) const { return g0 + (i & 15) < n; }
+};
+// One seat of a match (k_act_match32): the 32 rows of player `seat` of games
+// g0 .. g0 + 31, rows seat N + g0 + i.  The actions stay in LDS (no global
+// store: float2 rows of player 2 would sit at 8 N bytes, and nobody reads them).
+struct RowsSeat {
+  static constexpr bool kStore = false;
+  int64_t base, g0, n;  // base = seat N
+  __device__ int64_t operator()(int i) const { return base + g0 + i; }
+  __device__ bool valid(int i) const { return g0 + i < n; }
 };
 
 // one 32-row tile per workgroup of 4 waves: layer 1 n-tiles w, 4 + w,
@@ -1750,7 +1761,7 @@ __device__ __forceinline__ void actor_tile32(const Net& A, const char* __restric
         o0 += action_sd * z[0];
         o1 += action_sd * z[1];
       }
-      *(float2*)(out + row * 2) = make_float2(o0, o1);
+      if (MAP::kStore) *(float2*)(out + row * 2) = make_float2(o0, o1);
       if (act_lds) act_lds[i] = make_float2(o0, o1);
     }
   }
@@ -1937,6 +1948,93 @@ __global__ void __launch_bounds__(256) k_episode_finish(const int32_t* __restric
     step.slots[1 - step.parity] = step.slots[step.parity] + T;
     if (call_ctr) call_ctr[0] = call_ctr[0] + T;
   }
+}
+
+// Head-to-head evaluation (sk_env_act_match): two actors play whole matches
+// in ONE launch, seat 1 (player id 1) acting from net 1 and seat 2 from net
+// 2, without noise (SkillshotLearner.py:302-318 with two policies).  The
+// self-play tile (RowsPlayers) puts both players of 16 games in one MFMA tile,
+// so both share every weight fragment; here workgroup b owns the 32 games
+// 32b .. 32b + 31 and runs the tile twice per tick: the 32 player-1 rows
+// through net 1 (actions -> sAct[0..31]), the 32 player-2 rows through net 2
+// (-> sAct[32..63]).  Wave 0's 64 lanes are the (game, player) lanes of
+// k_step_split: split_load before the tiles (the state loads fly under both
+// MFMA chains), the episode kernel's loop test, split_finish after them.
+// LDS between the tiles: tile 1's layer 3 reads H2; tile 2 first writes S
+// (disjoint: tile 1's last S read, layer 1 of its second half, lies three
+// barriers back) and writes H1 (aliasing H2) only after its first
+// __syncthreads(), which every thread reaches after its layer 3 of tile 1.
+// sAct is read by wave 0 after the barrier that follows tile 2, and tile 1 of
+// tick t + 1 starts after the closing barrier of tick t.
+// Observations ping-pong in obs2 [2][2][N][12]: tick t reads half t & 1 and
+// writes half (t + 1) & 1 (this workgroup's own stores, ordered by the
+// closing barrier); no trajectory is recorded.  returns [2][N] (nullable) is
+// in/out: each (player, game) lane adds, in fp32 and in tick order, the
+// rewards of the ticks it played onto the value it found, so a match played
+// in several launches sums as one launch does.  split_finish stores the
+// tick's reward into the lane's own returns element, the lane reads it back
+// (its own store) and writes the sum at the end.  Counters: k_episode_finish
+// after this kernel, as for the episode (the step counter advances by
+// max_i lengths[i]); neither actor's noise call number is touched.
+struct MatchArgs {
+  float* obs2;
+  float* returns;
+  int32_t* lengths;
+  int32_t* last_half;
+  int n_ticks;
+};
+constexpr size_t kActMatchLds = kActorTileLds + 64 * sizeof(float2) + 16;
+__global__ void __launch_bounds__(kFwdThreads, SK_EPISODE_WAVES) k_act_match32(const float* __restrict__ aflat1,
+                                                                               const char* __restrict__ apack1,
+                                                                               const float* __restrict__ aflat2,
+                                                                               const char* __restrict__ apack2,
+                                                                               sk::StepArgs a, sk::Cfg c, MatchArgs mt) {
+  extern __shared__ __attribute__((aligned(16))) float smem_sl[];
+  char* smem = (char*)smem_sl;
+  float2* sAct = (float2*)(smem + kActorTileLds);
+  int* sAlive = (int*)(sAct + 64);
+  const int lane = threadIdx.x & 63;
+  const bool w0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0;
+  const int64_t g0 = (int64_t)blockIdx.x * 32;
+  sk_counters* const slot = nullptr;  // no episode counters (see k_act_episode32)
+  const int64_t n = a.n, gt = 2 * g0 + lane, gi = gt >> 1;  // wave 0: lane -> (game, player)
+  const bool mine = w0 && gi < n;
+  float* const ret = mine && mt.returns ? mt.returns + (int64_t)(lane & 1) * n + gi : nullptr;
+  float acc = ret ? *ret : 0.f;
+  if (mine && (lane & 1) == 0) mt.lengths[gi] = 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && mt.last_half) *mt.last_half = mt.n_ticks & 1;
+  for (int t = 0; t < mt.n_ticks; ++t) {
+    // both nets' addresses opaque per tick (k_act_episode32's reason, twice over)
+    const float *af1 = aflat1, *af2 = aflat2;
+    const char *pk1 = apack1, *pk2 = apack2;
+    asm volatile("" : "+s"(af1), "+s"(pk1), "+s"(af2), "+s"(pk2));
+    sk::StepArgs at = a;
+    at.acting_obs = mt.obs2 + (int64_t)(t & 1) * 24 * n;
+    at.obs = mt.obs2 + (int64_t)((t + 1) & 1) * 24 * n;
+    at.reward = mt.returns;
+    sk::StepLane L;
+    if (w0) L = sk::split_load(at, gt, slot);  // lanes past the tail: in = false
+    actor_tile32<false>(net_of(af1, kALd, 2), pk1, at.acting_obs, nullptr, RowsSeat{0, g0, n}, 0.f, 0.f, 0, 0,
+                        actor_lds(smem), sAct);
+    actor_tile32<false>(net_of(af2, kALd, 2), pk2, at.acting_obs, nullptr, RowsSeat{n, g0, n}, 0.f, 0.f, 0, 0,
+                        actor_lds(smem), sAct + 32);
+    if (w0) {
+      // the reference's loop test (:304) on the pre-tick state; both lanes of a game agree
+      const bool alive = L.in && ((L.mi.y >> 16) & 0xff) && L.mi.x < a.tick_limit;
+      L.in = alive;  // an ended game is neither stepped nor written
+      if (alive && L.p == 0) mt.lengths[L.i] = t + 1;
+      const uint64_t any = __ballot(alive);
+      if (lane == 0) *sAlive = any != 0;
+    }
+    __syncthreads();
+    if (!*sAlive) break;  // workgroup-uniform: every game of the workgroup has ended
+    if (w0) {
+      sk::split_finish(at, c, L, sAct[(lane & 1) * 32 + (lane >> 1)], slot);
+      if (L.in && ret) acc += *ret;  // the reward split_finish just stored for this (player, game)
+    }
+    __syncthreads();  // this tick's observations are the next tick's acting rows (this workgroup's own stores)
+  }
+  if (ret) *ret = acc;
 }
 
 // ---------------------------------------------------------------- actor forward, 16-row tiles
@@ -2337,6 +2435,25 @@ int sk_launch_act_episode32(const float* aflat, const void* apack, float sd, flo
   if (hipGetLastError() != hipSuccess) return SK_EHIP;
   const bool draws = (sd != 0.f || action_sd != 0.f) && call_ctr;
   k_episode_finish<<<1, 256, 0, st>>>(lengths, a.n, a.step, draws ? call_ctr : nullptr);
+  return hipGetLastError() == hipSuccess ? SK_OK : SK_EHIP;
+}
+
+// two actors' matches in one launch (sk_env_act_match, csrc/sk_engine.hip): any a.n >= 1
+int sk_launch_act_match32(const float* aflat1, const void* apack1, const float* aflat2, const void* apack2,
+                          const sk::StepArgs& a, const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths,
+                          int32_t* last_half, int n_ticks, hipStream_t st) {
+  static bool attr = false;
+  if (!attr) {
+    set_lds32(k_act_match32, kActMatchLds);
+    attr = true;
+  }
+  if (!apack1 || !apack2 || ((((uintptr_t)apack1) | ((uintptr_t)apack2)) & 15)) return SK_EINVAL;
+  const unsigned G = (unsigned)((a.n + 31) / 32);
+  const MatchArgs mt{obs2, returns, lengths, last_half, n_ticks};
+  k_act_match32<<<G, kFwdThreads, kActMatchLds, st>>>(aflat1, (const char*)apack1, aflat2, (const char*)apack2, a, c,
+                                                      mt);
+  if (hipGetLastError() != hipSuccess) return SK_EHIP;
+  k_episode_finish<<<1, 256, 0, st>>>(lengths, a.n, a.step, nullptr);
   return hipGetLastError() == hipSuccess ? SK_OK : SK_EHIP;
 }
 

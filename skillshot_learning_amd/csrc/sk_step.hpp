@@ -506,3 +506,7 @@ int sk_launch_act_step32(const float* aflat, const void* apack, float* act_out, 
 int sk_launch_act_episode32(const float* aflat, const void* apack, float sd, float action_sd, uint64_t seed,
                             uint64_t* call_ctr, const sk::StepArgs& a, const sk::Cfg& c, float* states,
                             float* actions, float* rewards, int32_t* lengths, int n_ticks, hipStream_t st);
+// k_act_match32 (csrc/sk_learn32.hip): two actors' whole matches, one launch
+int sk_launch_act_match32(const float* aflat1, const void* apack1, const float* aflat2, const void* apack2,
+                          const sk::StepArgs& a, const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths,
+                          int32_t* last_half, int n_ticks, hipStream_t st);

@@ -820,6 +820,31 @@ class DDPG:
             self._fused.rebind_optimisers()
 
 
+def match_outcomes(winner_id, seat):
+    """Outcome counts of finished games for the player in `seat` (1 or 2).
+    winner_id is the id of the player who was HIT (SkillshotGame.py:76-78),
+    not of the one who won: a hit on the opponent's seat (winner_id == 3 -
+    seat) is a win, a hit on the own seat a loss, 0 (the tick limit) a draw.
+    winner_id: a torch tensor (counts come back as 0-d tensors on its device,
+    no host sync) or any array-like (Python ints).  dict(wins, losses, draws)."""
+    if seat not in (1, 2):
+        raise ValueError("seat must be 1 or 2")
+    if torch.is_tensor(winner_id):
+        w = winner_id.long()
+        return dict(wins=(w == 3 - seat).sum(), losses=(w == seat).sum(), draws=(w == 0).sum())
+    w = np.asarray(winner_id).astype(np.int64)
+    return dict(wins=int((w == 3 - seat).sum()), losses=int((w == seat).sum()), draws=int((w == 0).sum()))
+
+
+def _match_summary(games, wins, losses, draws, ticks_sum, ret_self, ret_opp, seat=None):
+    d = dict(games=int(games), wins=int(wins), losses=int(losses), draws=int(draws),
+             win_rate=wins / games, loss_rate=losses / games, draw_rate=draws / games,
+             mean_ticks=ticks_sum / games, mean_return=ret_self / games, opponent_mean_return=ret_opp / games)
+    if seat is not None:
+        d["seat"] = seat
+    return d
+
+
 class SkillshotLearner:
     """Batched self-play DDPG learner (SkillshotLearner.py:13-682 API shape).
 
@@ -1076,6 +1101,154 @@ class SkillshotLearner:
         free, _ = torch.cuda.mem_get_info(self.device)
         per_tick = 120 * max(1, self.n_envs)
         return int(max(1, min(self.game_environment.tick_limit, (share * free) // per_tick)))
+
+    # ------------------------------------------------------------ evaluation
+    def evaluate(self, opponent=None, games=None, swap_sides=True, tick_limit=None, reward="looking", seed=None):
+        """Head-to-head evaluation: this learner's actor against `opponent`,
+        both deterministic (no exploration noise), over `games` whole games.
+
+        opponent  None (the learner's own actor: a mirror match, the sanity
+                  baseline), an Actor module, an actor state_dict, another
+                  SkillshotLearner, or an int checkpoint index under
+                  save_location (load_actor_critic_models' load_index; only
+                  the actor is read, into a net of its own)
+        games     games per leg (default n_envs); tick_limit (default the
+                  learner's) ends a game as a draw
+        swap_sides  play two legs from IDENTICAL start states, the learner in
+                  seat 1 (player id 1), then in seat 2: player 1 is
+                  hit-tested first (check_collision, SkillshotGame.py:58-94),
+                  and the swap cancels that seat bias
+        seed      of the evaluation env (default: derived from the learner's)
+
+        The games run on a dedicated evaluation env (created on first use,
+        kept per (games, tick_limit, seed)), rewound at every call: the same
+        call plays the same start positions (random when use_random_start),
+        so successive checkpoints face identical games.  Nothing of training
+        moves: the training env and its step counter, the actors' noise call
+        numbers, the replay ring and self.gen are left alone.
+
+        With the fp32 acting kernel on a GPU each leg is one launch
+        (VecSkillshotGame.act_match); otherwise, or with SK_MATCH_KERNEL=0, a
+        per-tick loop (the actors' forwards, step(auto_reset=False), ended
+        games masked as model_train's loop masks them) on either backend.
+        Outcomes are read off the final states once, at the end
+        (match_outcomes: winner_id is the id of the player who was HIT).
+
+        Returns dict(games, wins, losses, draws, win_rate, loss_rate,
+        draw_rate, mean_ticks, mean_return, opponent_mean_return, legs=[the
+        same fields per leg, plus seat]); the returns are per-game reward
+        sums of `reward` ("looking" / "simple")."""
+        n = int(self.n_envs if games is None else games)
+        limit = int(self.model_param_game_tick_limit if tick_limit is None else tick_limit)
+        g = self._eval_env(n, limit, seed)
+        mine, theirs = self._match_actors(opponent)
+        use_kernel = (self.precision == "fp32" and self.device.type == "cuda" and
+                      getattr(self.actor_kernel, "fused_act_step", False) and
+                      os.environ.get("SK_MATCH_KERNEL", "1") != "0")
+        g.step_counter = 0
+        g.reset(random_positions=self.use_random_start)
+        start = g.state_dict() if swap_sides else None
+        rows = []
+        for seat in ((1, 2) if swap_sides else (1,)):
+            if seat == 2:
+                g.load_state_dict(start)
+            a1, a2 = (mine, theirs) if seat == 1 else (theirs, mine)
+            obs, _ = g.observe(reward=reward)
+            if use_kernel:
+                m = g.act_match(a1[1], a2[1], obs, n_ticks=limit, reward=reward,
+                                out=getattr(g, "_match_bufs", None))
+                g._match_bufs = m
+                ret, winner, ticks = m["returns"], g.winner_id, g.ticks
+            else:
+                ret, winner, ticks = self._match_loop(g, a1[0], a2[0], obs, reward)
+            o = match_outcomes(winner, seat)
+            rows.append(torch.stack([v.double() for v in (o["wins"], o["losses"], o["draws"], ticks.sum(),
+                                                          ret[seat - 1].sum(), ret[2 - seat].sum())]))
+        flat = torch.stack(rows).cpu()  # the one host read: six scalars per leg
+        legs = [_match_summary(n, *flat[k].tolist(), seat=k + 1) for k in range(len(rows))]
+        total = _match_summary(n * len(rows), *flat.sum(0).tolist())
+        total["legs"] = legs
+        return total
+
+    def _eval_env(self, games, tick_limit, seed):
+        from .vec_env import VecSkillshotGame
+        tr = self.game_environment
+        s = int((tr.seed * 1000003 + 0x5EED) & ((1 << 63) - 1) if seed is None else seed)
+        envs = self.__dict__.setdefault("_eval_envs", {})
+        key = (games, tick_limit, s)
+        if key not in envs:
+            envs[key] = VecSkillshotGame(games, device=self.device, seed=s, env_offset=tr.env_offset,
+                                         tick_limit=tick_limit, random_positions=self.use_random_start)
+        return envs[key]
+
+    def _match_actors(self, opponent):
+        """(callable obs [M, 12] -> actions [M, 2], ActorKernel32 or None) of
+        the learner and of the opponent; an opponent's net and kernel are
+        built once per opponent object and kept"""
+        def pair(module, kernel):
+            if kernel is not None:
+                return (lambda x: kernel(x)), (kernel if getattr(kernel, "fused_act_step", False) else None)
+            return (lambda x: module(x)), None
+
+        mine = pair(self.model_actor, self.actor_kernel)
+        if opponent is None:
+            return mine, mine
+        if isinstance(opponent, SkillshotLearner):
+            if opponent.device == self.device and type(opponent.actor_kernel) is type(self.actor_kernel):
+                return mine, pair(opponent.model_actor, opponent.actor_kernel)
+            opponent = opponent.model_actor
+        cache = self.__dict__.setdefault("_eval_opponents", {})
+        if isinstance(opponent, bool) or not isinstance(opponent, (int, np.integer, dict, nn.Module)):
+            raise TypeError("opponent: None, an Actor, an actor state_dict, a SkillshotLearner or a checkpoint index")
+        if isinstance(opponent, (int, np.integer)):
+            key = ("checkpoint", int(opponent))
+        else:
+            key = ("object", id(opponent))
+        ent = cache.get(key)
+        if ent is None or (key[0] == "object" and ent["source"] is not opponent):
+            # a net of evaluate's own (the caller's object is only read: the
+            # fp32 kernel would re-seat its parameters in a flat buffer)
+            with torch.random.fork_rng(devices=[]):  # Actor() draws its initial weights
+                net = Actor().to(self.device)
+            kernel = type(self.actor_kernel)(net, seed=0) if self.actor_kernel is not None else None
+            while len(cache) >= 8:  # (state_dicts made afresh per call would pile up)
+                cache.pop(next(iter(cache)))
+            ent = cache[key] = dict(source=opponent, net=net, kernel=kernel)
+        net = ent["net"]
+        with torch.no_grad():  # the weights are copied at every call: the opponent may have trained since
+            if isinstance(opponent, (int, np.integer)):
+                from . import persist
+                if not persist.load_actor(self.save_location, net, int(opponent)):
+                    raise SkillshotError(f"no saved actor under {self.save_location}")
+            elif isinstance(opponent, dict):
+                net.load_state_dict({k: torch.as_tensor(v).to(self.device) for k, v in opponent.items()})
+            else:
+                net.load_state_dict({k: v.to(self.device) for k, v in opponent.state_dict().items()})
+        if getattr(ent["kernel"], "buf", None) is not None:
+            ent["kernel"].refresh()  # the bf16 forward pack does not follow its module
+        return mine, pair(net, ent["kernel"])
+
+    @torch.no_grad()
+    def _match_loop(self, g, act1, act2, obs, reward):
+        """one leg tick by tick on env g: seat 1 acts with act1, seat 2 with
+        act2; returns (fp32 reward sums [2, N] over each game's own ticks, the
+        games' final winner_id and ticks).  step(auto_reset=False) keeps
+        moving the players of ended games, so an ended game's outcome is kept
+        from the tick it ended on (model_train's masking, :302-318)."""
+        n, dev = g.n, g.device
+        alive = g.game_live & (g.ticks < g.tick_limit)
+        acc = torch.zeros((2, n), dtype=torch.float32, device=dev)
+        ticks, winner = g.ticks.clone(), g.winner_id.clone()
+        while bool(alive.any()):
+            act = torch.stack((act1(obs[0]), act2(obs[1])))
+            out = g.step(act, obs=True, reward=reward, auto_reset=False)
+            acc = torch.where(alive[None, :], acc + out["reward"], acc)
+            newly = alive & out["done"].bool()
+            ticks = torch.where(newly, g.ticks, ticks)
+            winner = torch.where(newly, out["winner"], winner)
+            alive = alive & ~out["done"].bool()
+            obs = out["obs"]
+        return acc, winner, ticks
 
     # ------------------------------------------------------------ on-disk formats (persist.py)
     def save_actor_critic_models(self, epochs):

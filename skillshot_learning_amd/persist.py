@@ -72,6 +72,25 @@ def load_actor_critic_models(save_location, actor, critic, load_index=-1):
     return True
 
 
+def load_actor(save_location, actor, load_index=-1):
+    """Only the actor of a saved pair, into `actor` (load_index as in
+    load_actor_critic_models): the opponent of SkillshotLearner.evaluate,
+    loaded without touching the learner's own nets.  False (after printing
+    the location) if none is saved."""
+    from safetensors.torch import load_file
+    loc = os.path.join(save_location, ACTOR_DIR)
+    files = _epoch_sorted([f for f in os.listdir(loc) if f.endswith("_model.safetensors")]) \
+        if os.path.isdir(loc) else []
+    if not files:
+        print("Failed to load: ", loc)
+        return False
+    state = load_file(os.path.join(loc, files[load_index]))
+    dev = next(actor.parameters()).device
+    with torch.no_grad():
+        actor.load_state_dict({k: v.to(dev) for k, v in state.items()})
+    return True
+
+
 def progress_frame(total_progress):
     """One row per (epoch, game): epoch, game, epoch_ticks, epoch_winner."""
     import pandas as pd

@@ -467,6 +467,60 @@ class VecSkillshotGame:
                                          _ptr(actor._ctr), REWARD_KINDS[reward], self.tick_limit, self._stream()))
         return dict(states=st[:T + 1], actions=ac[:T], rewards=rw[:T], lengths=ln)
 
+    def act_match(self, actor1, actor2, start_obs, n_ticks=None, reward="looking", out=None, resume=False):
+        """Two actors play every game head to head in ONE launch
+        (sk_env_act_match; the loop of SkillshotLearner.py:302-318 with two
+        policies): seat 1 (player id 1) acts from actor1, seat 2 from actor2
+        (both ActorKernel32), without exploration noise, until each game ends
+        (hit or tick limit) or n_ticks ticks (default: the tick limit) have
+        run.  start_obs [2, N, 12]: the observation of the current state.
+        Returns dict(lengths int32 [N], the ticks each game played; returns
+        [2, N], each player's fp32 reward sum in tick order; obs [2, N, 12],
+        every game's newest observation — of its final state once it has
+        ended — plus the launch's buffers).  An ended game is not stepped
+        again, so the env's planes hold the final states: winner_id is the id
+        of the player who was HIT.  A game still live after n_ticks continues
+        with act_match(..., start_obs=prev["obs"], out=prev, resume=True):
+        lengths and returns then carry on from `prev` (the sums equal one
+        long launch's, bit for bit).  out without resume only reuses the
+        buffers.  The device step counter advances by max(lengths of this
+        call); neither actor's noise call number moves.  Any N >= 1."""
+        if self.is_cpu:
+            raise SkillshotError("act_match runs on the GPU backend (SkillshotLearner.evaluate loops on the CPU one)")
+        T = int(self.tick_limit if n_ticks is None else n_ticks)
+        o = out or {}
+        if resume and (o.get("returns") is None or o.get("lengths") is None):
+            raise ValueError("resume needs the dict a previous act_match returned as out")
+
+        def buf(key, shape, dtype):
+            t = o.get(key)
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=self.device)
+            elif tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"out[{key!r}] must be contiguous {dtype} {shape} on {self.device}")
+            return t
+
+        start = start_obs.reshape(2, self.n, 12)  # (may be out["obs"]: read before it is rewritten)
+        obs2 = buf("obs2", (2, 2, self.n, 12), torch.float32)
+        ret = buf("returns", (2, self.n), torch.float32)
+        call_ln = buf("call_lengths", (self.n,), torch.int32)
+        total = buf("lengths", (self.n,), torch.int32)
+        obs = buf("obs", (2, self.n, 12), torch.float32)
+        obs2[0].copy_(start)
+        if not resume:
+            ret.zero_()
+        p1, p2 = actor1.ensure_pack(), actor2.ensure_pack()
+        check(self._L.sk_env_act_match(self._h, _ptr(actor1.flat), _ptr(p1), _ptr(actor2.flat), _ptr(p2), _ptr(obs2),
+                                       _ptr(ret), _ptr(call_ln), _ptr(o.get("last_half")), T,
+                                       REWARD_KINDS[reward], self.tick_limit, self._stream()))
+        torch.where((call_ln & 1).bool()[None, :, None], obs2[1], obs2[0], out=obs)
+        if resume:
+            total += call_ln
+        else:
+            total.copy_(call_ln)
+        return dict(lengths=total, returns=ret, obs=obs, obs2=obs2, call_lengths=call_ln,
+                    last_half=o.get("last_half"))
+
     def step_raw(self, actions_ptr, done_ptr=None, obs_ptr=None, reward_ptr=None, winner_ptr=None,
                  auto_reset=True, stream=None):
         """Pointer-level fused step (bench / graph capture; no allocation)."""
