@@ -22,6 +22,12 @@
 //                         per player and plane), the default from 40,960 to
 //                         98,304 games, there in long launches on fp32 trig
 //                         with the wave's exact fallback (FAST)
+//                         The packed launch is peeled: tick 0 and the
+//                         last tick on the generic tick, between them a
+//                         steady loop that knows its state form at compile
+//                         time (split_tick_carry's STEADY form), 32-bit
+//                         offsets into the ring and the output rows, and
+//                         (FAST) a rest between its stores and its reload
 //     both run the carried-sincos tick: tick_env_carry (sk_device.hpp) and
 //     split_tick_carry (below)
 //   k_rollout_random      n ticks of the random policy in one launch, state
@@ -148,6 +154,8 @@ static constexpr int64_t kSplitPackMaxEnvs = 98304;
 // fp64 carry runs under the loads for nothing
 // (profiles/r09_split_fast_sweep.jsonl)
 static constexpr int kFastSplitMinTicks = 100;
+// the steady loop's rest between a tick's stores and the next tick's loads, in units of 64 cycles (k_step_split_multi)
+static constexpr int kSteadyRest = 7;
 // SK_CTR_STRIDE slots per wave of the widest step grid (k_step_split: two
 // lanes per game), at least SK_COUNTER_SLOTS
 static inline int64_t counter_slots(int64_t n) {
@@ -501,6 +509,7 @@ struct MultiArgs {
   int64_t ring;           // slabs in the ring
   int64_t slab0;          // slab of tick 0 (< ring)
   int n_ticks;
+  int steady32;           // the packed split kernel's steady loop may run (split_steady_fits32); in n_ticks' padding
   uint8_t* done;          // tick t writes done + t * out_stride (nullable)
   uint8_t* winner;        // same (nullable)
   int64_t out_stride;
@@ -1124,6 +1133,16 @@ __device__ __forceinline__ void split_carry_advance(SplitCarryF& t) {
   t.have = true;
   t.pend = false;
 }
+// The advanced carry pinned where it stands (empty asms).  The steady loop
+// advances unconditionally, and without this the evaluation is sunk past the
+// loads' wait into the tick's no-miss branch, onto the chain it was taken off
+// (the generic tick's `if (tc.pend)` block keeps it in place by itself).
+__device__ __forceinline__ void split_carry_pin(SplitCarry& t) {
+  asm volatile("" : "+v"(t.m.s), "+v"(t.m.c), "+v"(t.tq.s), "+v"(t.tq.c));
+}
+__device__ __forceinline__ void split_carry_pin(SplitCarryF& t) {
+  asm volatile("" : "+v"(t.m.s), "+v"(t.m.c));
+}
 template <bool FAST>
 struct SplitCarrySel {
   using type = SplitCarry;
@@ -1228,14 +1247,30 @@ __device__ __forceinline__ void split_store_pack(const MultiArgs& a, __amdgpu_bu
 // fast range or whose action is not finite evaluates sincos_bf (the library
 // past its range) and takes the fp64 expressions of the other form: the same
 // result bit for bit, about one wave-tick in a few hundred.
-template <int POL, bool OBS, bool PACK = false, bool FAST = false>
+//
+// STEADY (PACK only): the tick of the packed kernel's steady loop
+// (k_step_split_multi).  Known at compile time: the state arrives packed,
+// the tick is not the launch's last, the carry is valid.  What is left of the
+// form tests is the wave's one `fit` ballot (a wave that stops fitting stores
+// the exchange format and leaves the loop).  The done / winner rows go
+// through buffer resources at 32-bit offsets (SplitSteady), and the episode
+// counts and the restart sit behind one ballot of `done`: a wave of 32 games
+// has a finished one in about one tick in forty.
+struct SplitSteady {
+  __amdgpu_buffer_rsrc_t ra, rd, rw;  // the action ring, done, winner (a NULL output: no records, its stores are dropped)
+  uint32_t va, vd;                    // this lane's byte offset in an action slab / an output row
+  uint32_t aso, dso;                  // the next tick's slab and this tick's output row, in bytes (wave-uniform)
+};
+template <int POL, bool OBS, bool PACK = false, bool FAST = false, bool STEADY = false>
 __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& c, __amdgpu_buffer_rsrc_t r,
                                                  SplitLane& L, WaveCtr& wc, int64_t so, uint64_t step,
                                                  const SplitRaw& w, float2 act,
                                                  typename SplitCarrySel<FAST>::type& tc, bool last,
-                                                 __amdgpu_buffer_rsrc_t rp, bool& packed) {
+                                                 __amdgpu_buffer_rsrc_t rp, bool& packed,
+                                                 const SplitSteady* ss = nullptr) {
   static_assert(!(OBS && PACK), "the full contract never packs");
   static_assert(!(OBS && FAST), "the observation needs the exact sincos");
+  static_assert(PACK || !STEADY, "the steady loop is the packed kernel's");
   using sktrig::round_safe;
   const int p = L.p;
   double rot = __builtin_bit_cast(double, w.rot), qrot = __builtin_bit_cast(double, w.qrot);
@@ -1243,7 +1278,7 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
   const unsigned flags = (unsigned)w.mi.y;
   int qvalid = (flags >> (8 * p)) & 0xff, live = (flags >> 16) & 0xff, winner = (flags >> 24) & 0xff;
   if constexpr (PACK) {
-    if (packed) {  // w.pp: {pack_pos, pack_cah} of this lane's player
+    if (STEADY || packed) {  // w.pp: {pack_pos, pack_cah} of this lane's player
       const unsigned s = (unsigned)w.pp.x, ch = (unsigned)w.pp.y;
       px = s & 0xff; py = (s >> 8) & 0xff; qx = (s >> 16) & 0xff; qy = s >> 24;
       qcd = (int)(signed char)(ch & 0xff); qage = (ch >> 8) & 0xff;
@@ -1255,7 +1290,7 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
   }
   const double q_old = qrot;
   const bool f = qcd <= 0;  // fires this tick (Player.py:80)
-  const bool miss = !tc.have || !same_bits(rot, tc.kr) || (qvalid && !f && !same_bits(qrot, tc.kq));
+  const bool miss = (!STEADY && !tc.have) || !same_bits(rot, tc.kr) || (qvalid && !f && !same_bits(qrot, tc.kq));
   if (__ballot(L.in && miss) != 0) {  // the launch's first tick
     if constexpr (FAST) {
       bool kq;
@@ -1418,21 +1453,23 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
     winner = h1 ? 1 : (h2 ? 2 : winner);
     live = (h1 || h2) ? 0 : live;
   }
-  ctr_settle(wc);  // every load of this tick consumed (see multi_tick)
+  // every load of this tick consumed (see multi_tick); a steady tick is never
+  // the launch's last, and the generic tick that is settles the slot
+  if constexpr (!STEADY) ctr_settle(wc);
   bool to_pack = false;
   if constexpr (PACK) {
     const bool fit = !L.in || ((int)pack_fits_player(px, py, qx, qy, qcd, qage, qvalid) &
                                (int)pack_fits_game(ticks, live, winner));
-    to_pack = !last && __ballot(!fit) == 0;  // wave-uniform
+    to_pack = (STEADY || !last) && __ballot(!fit) == 0;  // wave-uniform
   }
   if (PACK && to_pack) {  // the packed halves out before done / restart
-    const bool qch = !packed || __double_as_longlong(qrot) != __double_as_longlong(q_old);
+    const bool qch = (!STEADY && !packed) || __double_as_longlong(qrot) != __double_as_longlong(q_old);
     const unsigned hi = p ? pack_flags(oqv, qvalid, live, winner) : (unsigned)ticks;
     if (L.in) split_store_pack<POL>(a, rp, L, rot, qrot, qch, pack_pos(px, py, qx, qy), pack_cah(qcd, qage, hi));
   } else {  // the state out before done / restart (multi_compute's early store, for its reason)
     const unsigned fl = (unsigned)(qvalid & 0xff) | ((unsigned)(oqv & 0xff) << 8) | ((unsigned)(live & 0xff) << 16) |
                         ((unsigned)(winner & 0xff) << 24);
-    const bool qch = (PACK && packed) || __double_as_longlong(qrot) != __double_as_longlong(q_old);
+    const bool qch = STEADY || (PACK && packed) || __double_as_longlong(qrot) != __double_as_longlong(q_old);
     if (L.in) split_store_state<POL>(a, r, L, px, py, rot, qx, qy, qrot, qch, qcd, qage, ticks, fl);
   }
   bool amb = false;
@@ -1459,35 +1496,44 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
   }
   const bool d = L.in && ((!live) || (ticks >= a.tick_limit));  // SkillshotLearner.py:302
   if (L.in && p == 0) {
-    if (a.done) a.done[so * a.out_stride + L.i] = (uint8_t)d;
-    if (a.winner) a.winner[so * a.out_stride + L.i] = (uint8_t)winner;
-  }
-  const bool dc = d && p == 0;
-  L.n_done += dc;
-  L.n_h1 += dc && winner == 1;
-  L.n_h2 += dc && winner == 2;
-  L.t_sum += dc ? (unsigned)ticks : 0u;
-  const bool rs = d && a.auto_reset;  // SkillshotGame.__init__ :10-25 for this lane's player
-  if (rs) {
-    if (a.random_positions) {
-      const U4 u4 = draw4(a.seed, (uint64_t)(a.env_offset + L.i), step, 1u);
-      px = u32_to_pos(p ? u4.z : u4.x, c.rlo, c.rhi);
-      py = u32_to_pos(p ? u4.w : u4.y, c.rlo, c.rhi);
+    if constexpr (STEADY) {
+      __builtin_amdgcn_raw_buffer_store_b8((unsigned char)d, ss->rd, ss->vd, ss->dso, 0);
+      __builtin_amdgcn_raw_buffer_store_b8((unsigned char)winner, ss->rw, ss->vd, ss->dso, 0);
     } else {
-      px = p ? c.f2x : c.f1x;
-      py = p ? c.f2y : c.f1y;
+      if (a.done) a.done[so * a.out_stride + L.i] = (uint8_t)d;
+      if (a.winner) a.winner[so * a.out_stride + L.i] = (uint8_t)winner;
     }
-    rot = 0.0; qx = 0; qy = 0; qrot = 0.0; qcd = 0; qage = 0; qvalid = 0;
-    ticks = 0; live = 1; winner = 0;
   }
-  const int ov = pair_swap(qvalid);  // every lane active (top level)
-  if (PACK && to_pack) {
-    const unsigned hi = p ? pack_flags(ov, qvalid, live, winner) : (unsigned)ticks;
-    if (rs) split_store_pack<POL>(a, rp, L, rot, qrot, true, pack_pos(px, py, qx, qy), pack_cah(qcd, qage, hi));
-  } else if (rs) {
-    const unsigned fl = (unsigned)(qvalid & 0xff) | ((unsigned)(ov & 0xff) << 8) | ((unsigned)(live & 0xff) << 16) |
-                        ((unsigned)(winner & 0xff) << 24);
-    split_store_state<POL>(a, r, L, px, py, rot, qx, qy, qrot, true, qcd, qage, ticks, fl);
+  bool any_done = true, rs = false;
+  if constexpr (STEADY) any_done = __ballot(d) != 0;  // wave-uniform: the counts stay exact
+  if (any_done) {
+    const bool dc = d && p == 0;
+    L.n_done += dc;
+    L.n_h1 += dc && winner == 1;
+    L.n_h2 += dc && winner == 2;
+    L.t_sum += dc ? (unsigned)ticks : 0u;
+    rs = d && a.auto_reset;  // SkillshotGame.__init__ :10-25 for this lane's player
+    if (rs) {
+      if (a.random_positions) {
+        const U4 u4 = draw4(a.seed, (uint64_t)(a.env_offset + L.i), step, 1u);
+        px = u32_to_pos(p ? u4.z : u4.x, c.rlo, c.rhi);
+        py = u32_to_pos(p ? u4.w : u4.y, c.rlo, c.rhi);
+      } else {
+        px = p ? c.f2x : c.f1x;
+        py = p ? c.f2y : c.f1y;
+      }
+      rot = 0.0; qx = 0; qy = 0; qrot = 0.0; qcd = 0; qage = 0; qvalid = 0;
+      ticks = 0; live = 1; winner = 0;
+    }
+    const int ov = pair_swap(qvalid);  // every lane active (top level, or under the wave-uniform ballot)
+    if (PACK && to_pack) {
+      const unsigned hi = p ? pack_flags(ov, qvalid, live, winner) : (unsigned)ticks;
+      if (rs) split_store_pack<POL>(a, rp, L, rot, qrot, true, pack_pos(px, py, qx, qy), pack_cah(qcd, qage, hi));
+    } else if (rs) {
+      const unsigned fl = (unsigned)(qvalid & 0xff) | ((unsigned)(ov & 0xff) << 8) | ((unsigned)(live & 0xff) << 16) |
+                          ((unsigned)(winner & 0xff) << 24);
+      split_store_state<POL>(a, r, L, px, py, rot, qx, qy, qrot, true, qcd, qage, ticks, fl);
+    }
   }
   if constexpr (PACK) packed = to_pack;
   if constexpr (OBS) {
@@ -1506,7 +1552,7 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
     tc.tq = tq_obs;
     tc.kq = qrot;
     tc.have = true;
-  } else if (!last) {  // the tick's final rotation: the next tick's carried sincos
+  } else if (STEADY || !last) {  // the tick's final rotation: the next tick's carried sincos
     tc.pr = rot;
     if constexpr (!FAST) tc.qs = same_bits(qrot, rot);
     tc.pend = true;
@@ -1577,11 +1623,99 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
     pslab = pslab + 1 == a.ring ? 0 : pslab + 1;
     so = so + 1 == a.out_slabs ? 0 : so + 1;
   };
-  do {  // n_ticks >= 1 (host-checked)
-    one_tick(pa0, pa1);
-    if (++t >= a.n_ticks) break;
-    one_tick(pa1, pa0);
-  } while (++t < a.n_ticks);
+  if constexpr (PACK) {
+    // The launch peeled: tick 0 (exchange format in) and the last tick
+    // (exchange format out) run the generic tick above; between them, while
+    // the wave fits the packed form, the steady loop: packed in and out, not
+    // the last tick, the carry pending (split_tick_carry's STEADY form), the
+    // ring and the output rows at 32-bit byte offsets (a.steady32: the host
+    // checked that they fit) with one scalar add and compare each per tick.
+    // A wave whose ballot fails leaves for the generic tick and comes back
+    // at the next odd tick at which it is packed again.
+    SplitSteady S;
+    const uint32_t slab_b = (uint32_t)a.n * 16u, ring_b = (uint32_t)a.ring * slab_b;
+    const uint32_t out_b = (uint32_t)a.out_slabs * (uint32_t)a.out_stride;
+    S.ra = __builtin_amdgcn_make_buffer_rsrc(const_cast<float2*>(a.actions), (short)0, (int)ring_b, 0x00020000);
+    // (readfirstlane: the record counts in SGPRs, or the stores get a waterfall loop)
+    S.rd = __builtin_amdgcn_make_buffer_rsrc(a.done, (short)0, __builtin_amdgcn_readfirstlane(a.done ? -1 : 0),
+                                             0x00020000);
+    S.rw = __builtin_amdgcn_make_buffer_rsrc(a.winner, (short)0, __builtin_amdgcn_readfirstlane(a.winner ? -1 : 0),
+                                             0x00020000);
+    S.va = (uint32_t)aoff * 8u;
+    S.vd = (uint32_t)L.ic;
+    S.aso = S.dso = 0;
+    auto steady_tick = [&](const float2& cur, float2& nxt) {
+      SplitRaw w;
+      split_load_pack<POL>(a, rp, L, w);
+      const skb2i na = __builtin_amdgcn_raw_buffer_load_b64(S.ra, S.va, S.aso, 2);  // nontemporal, as load_action
+      nxt = make_float2(__int_as_float(na.x), __int_as_float(na.y));
+      __builtin_amdgcn_sched_barrier(0);
+      split_carry_advance(tc);  // the last tick's rotation, while this tick's loads fly
+      split_carry_pin(tc);
+      __builtin_amdgcn_sched_barrier(0);
+      split_tick_carry<POL, false, true, FAST, true>(a, c, r, L, wc, 0, step0 + (uint64_t)t, w, cur, tc, false, rp,
+                                                     packed, &S);
+      // The wave rests kSteadyRest x 64 cycles between its stores and the
+      // next tick's loads of the same lines.  With the loop's shorter tail
+      // the reload followed the write-through stores within ~50 instructions
+      // and waited far longer for them (1.89-1.90 us per tick against the
+      // parent's 1.74-1.77: fewer slots, more wait); the generic tick's
+      // done / store maze had kept the two apart.  A sleeping wave leaves
+      // the issue port to its partner, which filler instructions would not
+      // (0: 1.89, 3: 1.77, 4: 1.72, 5: 1.68, 6: 1.66-1.67, 7: 1.65-1.66,
+      // 10: 1.71 us; profiles/r11_steady_rest_sweep.txt).  The fp64-carry
+      // form (the launches under kFastSplitMinTicks ticks) does not rest: its
+      // 20-tick launch reads the parent's figure without, and 3.7 % more with
+      // (profiles/r11_bench_ab_norest.jsonl, r11_bench_ab_rest_both.jsonl).
+      if constexpr (FAST) __builtin_amdgcn_s_sleep(kSteadyRest);
+      S.aso = S.aso + slab_b == ring_b ? 0u : S.aso + slab_b;
+      S.dso = S.dso + (uint32_t)a.out_stride == out_b ? 0u : S.dso + (uint32_t)a.out_stride;
+    };
+    do {  // n_ticks >= 1 (host-checked); t is even here and this tick's actions are in pa0
+      one_tick(pa0, pa1);
+      if (++t >= a.n_ticks) break;
+      bool odd = true;
+      if (a.steady32 && packed && t + 2 < a.n_ticks) {
+        const int t_in = t;
+        const uint32_t slab_in = (uint32_t)slab, so_in = (uint32_t)so;
+        S.aso = (uint32_t)pslab * slab_b;
+        S.dso = so_in * (uint32_t)a.out_stride;
+        // The loop's own action pair, cut from pa0 / pa1 by empty asms at its
+        // entry and exit: sharing their registers left a copy of the pair on
+        // the back edge, behind an s_waitcnt vmcnt(0), i.e. every second tick
+        // waited for the wave's own state stores to be acknowledged.
+        float2 sa0 = pa0, sa1 = pa1;
+        asm volatile("" : "+v"(sa1.x), "+v"(sa1.y));
+        do {  // two steady ticks per turn: neither is the launch's last
+          steady_tick(sa1, sa0);
+          ++t;
+          odd = packed;  // (no break out of the middle: its edge shared the latch's block, and the copy came back)
+          if (odd) {
+            steady_tick(sa0, sa1);
+            ++t;
+          }
+        } while (packed && t + 2 < a.n_ticks);
+        pa0 = sa0;
+        pa1 = sa1;
+        asm volatile("" : "+v"(pa0.x), "+v"(pa0.y), "+v"(pa1.x), "+v"(pa1.y));
+        // back to the generic tick's 64-bit ring positions (steady32: both fit 32 bits)
+        const uint32_t dt = (uint32_t)(t - t_in);
+        slab = (int64_t)((slab_in + dt) % (uint32_t)a.ring);
+        pslab = slab + 1 == a.ring ? 0 : slab + 1;
+        so = (int64_t)((so_in + dt) % (uint32_t)a.out_slabs);
+      }
+      if (odd) {
+        one_tick(pa1, pa0);
+        ++t;
+      }
+    } while (t < a.n_ticks);
+  } else {
+    do {  // n_ticks >= 1 (host-checked)
+      one_tick(pa0, pa1);
+      if (++t >= a.n_ticks) break;
+      one_tick(pa1, pa0);
+    } while (++t < a.n_ticks);
+  }
   if (a.ctr) {
     const unsigned c4[4] = {L.n_done, L.n_h1, L.n_h2, L.t_sum};
     uint64_t v[4];
@@ -2462,6 +2596,26 @@ int sk_env_act_step_job(sk_env* e, const float* actor_flat, const void* actor_pa
   return SK_OK;
 }
 
+// The packed split kernel's steady loop addresses the action ring and the
+// done / winner rows with 32-bit byte offsets off a buffer resource: every
+// slab of the ring (ring_slabs x 16 n bytes) and every output row
+// (out_slabs x out_stride, plus a row's n bytes) must lie below 4 GiB, and
+// both ring positions must fit an int.  A launch outside these bounds keeps
+// the generic tick's 64-bit addressing for all of its ticks (MultiArgs::
+// steady32 = 0): same results.
+static bool split_steady_fits32(int64_t n, int64_t ring_slabs, int64_t out_slabs, int64_t out_stride) {
+  const uint64_t lim = 0xffffffffull;
+  if (n <= 0 || ring_slabs <= 0 || out_slabs <= 0 || out_stride < 0) return false;
+  if ((uint64_t)n > lim / 16u || (uint64_t)ring_slabs > lim / (16u * (uint64_t)n)) return false;
+  if ((uint64_t)out_slabs > 0x7fffffffull) return false;
+  if (out_stride > 0 && (uint64_t)out_slabs > (lim - (uint64_t)n) / (uint64_t)out_stride) return false;
+  return true;
+}
+// the size arithmetic alone, for the tests (no device needed)
+extern "C" int skdiag_split_steady_fits32(int64_t n, int64_t ring_slabs, int64_t out_slabs, int64_t out_stride) {
+  return split_steady_fits32(n, ring_slabs, out_slabs, out_stride) ? 1 : 0;
+}
+
 // sk_env_step_multi (obs == reward == NULL, full == false) and
 // sk_env_step_multi_obs (full == true: the split geometry with the obs /
 // reward epilogue, k_step_split_multi<POL, BLK, true>)
@@ -2501,6 +2655,7 @@ static int step_multi(sk_env* e, const float* actions, int64_t ring_slabs, int64
   a.ring = ring_slabs;
   a.slab0 = slab0;
   a.n_ticks = n_ticks;
+  a.steady32 = split_steady_fits32(e->n, ring_slabs, out_slabs, out_stride) ? 1 : 0;
   a.done = done;
   a.winner = winner;
   a.out_stride = out_stride;
