@@ -27,7 +27,9 @@
 //                         steady loop that knows its state form at compile
 //                         time (split_tick_carry's STEADY form), 32-bit
 //                         offsets into the ring and the output rows, and
-//                         (FAST) a rest between its stores and its reload
+//                         (FAST) the tick's state-independent arithmetic
+//                         under its loads (SplitPre) and a rest between its
+//                         stores and its reload
 //     both run the carried-sincos tick: tick_env_carry (sk_device.hpp) and
 //     split_tick_carry (below)
 //   k_rollout_random      n ticks of the random policy in one launch, state
@@ -1261,13 +1263,58 @@ struct SplitSteady {
   uint32_t va, vd;                    // this lane's byte offset in an action slab / an output row
   uint32_t aso, dso;                  // the next tick's slab and this tick's output row, in bytes (wave-uniform)
 };
+// The part of the FAST tick that reads no loaded state, only the carried
+// sincos_fast of the rotation, the action and the configuration: the clamped
+// look action and its rotation step, the fired projectile's angle addition
+// and step, the move's deltas, their round_safe decisions and the rounded
+// integers.  The steady loop evaluates it under its loads (split_pre_pin
+// keeps it there, as split_carry_pin the carry); the tick combines the fired
+// step's safety with `f` after the wait.  The same expressions on the same
+// inputs as the generic tick's, so the same bits.
+struct SplitPre {
+  float l;            // the clamped look action
+  double dl;          // (double)l * look: the rotation's step
+  sktrig::SinCosF u;  // sincos_fast(rotation + l * look) by angle addition
+  float ex, ey;       // a fired projectile's step
+  float mdx, mdy;     // the move's deltas
+  bool msafe, qsafe;  // fast_move_delta's / the fired step's `safe`
+  int imx, imy, iex, iey;  // rintf of the deltas and of the step
+};
+__device__ __forceinline__ SplitPre split_fast_pre(const sktrig::SinCosF& m, bool mok, float2 act, const Cfg& c) {
+  SplitPre q;
+  const float qsf = (float)c.qspeed;
+  q.l = clamp_action_f(act.y);
+  q.dl = (double)q.l * c.look;
+  q.u = sktrig::sincos_add(m, q.l * (float)c.look);
+  q.ex = q.u.s * qsf;
+  q.ey = q.u.c * qsf;
+  const sktrig::FastDelta dm = sktrig::fast_move_delta(m, mok, (float)c.pspeed, clamp_action_f(act.x));
+  q.mdx = dm.x;
+  q.mdy = dm.y;
+  q.msafe = dm.safe;
+  q.qsafe = sktrig::fast_step_delta(q.u, mok, qsf).safe;  // its deltas are ex, ey
+  q.imx = (int)rintf(q.mdx);
+  q.imy = (int)rintf(q.mdy);
+  q.iex = (int)rintf(q.ex);
+  q.iey = (int)rintf(q.ey);
+  return q;
+}
+// (the two decisions are pinned as the lane masks they are: every lane of the
+// wave is active where the steady loop evaluates them)
+__device__ __forceinline__ void split_pre_pin(SplitPre& q) {
+  unsigned long long ms = __builtin_amdgcn_ballot_w64(q.msafe), qs = __builtin_amdgcn_ballot_w64(q.qsafe);
+  asm volatile("" : "+v"(q.dl), "+v"(q.imx), "+v"(q.imy), "+v"(q.iex), "+v"(q.iey), "+s"(ms), "+s"(qs));
+  q.msafe = __builtin_amdgcn_inverse_ballot_w64(ms);
+  q.qsafe = __builtin_amdgcn_inverse_ballot_w64(qs);
+}
 template <int POL, bool OBS, bool PACK = false, bool FAST = false, bool STEADY = false>
 __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& c, __amdgpu_buffer_rsrc_t r,
                                                  SplitLane& L, WaveCtr& wc, int64_t so, uint64_t step,
                                                  const SplitRaw& w, float2 act,
                                                  typename SplitCarrySel<FAST>::type& tc, bool last,
                                                  __amdgpu_buffer_rsrc_t rp, bool& packed,
-                                                 const SplitSteady* ss = nullptr) {
+                                                 const SplitSteady* ss = nullptr, SplitPre* pre = nullptr) {
+  constexpr bool PRE = FAST && STEADY;  // the state-independent part arrives evaluated (SplitPre)
   static_assert(!(OBS && PACK), "the full contract never packs");
   static_assert(!(OBS && FAST), "the observation needs the exact sincos");
   static_assert(PACK || !STEADY, "the steady loop is the packed kernel's");
@@ -1312,20 +1359,28 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
     tc.kr = rot;
     tc.kq = qrot;
     tc.have = true;
+    if constexpr (PRE) *pre = split_fast_pre(tc.m, tc.mok, act, c);  // off the refreshed carry
   }
-  const float l = clamp_action_f(act.y);
-  const double rn = rot + (double)l * c.look;  // == move_look_s
+  SplitPre q{};
+  if constexpr (PRE) q = *pre;
+  const float l = PRE ? q.l : clamp_action_f(act.y);
+  const double rn = rot + (PRE ? q.dl : (double)l * c.look);  // == move_look_s
   const float lk = (float)c.look, qsf = (float)c.qspeed, eq = 2e-6f * qsf;
   sktrig::SinCosF mf;
   if constexpr (FAST) mf = tc.m;
   else mf = sktrig::SinCosF{(float)tc.m.s, (float)tc.m.c};
-  const sktrig::SinCosF u = sktrig::sincos_add(mf, l * lk);
-  const float ex = u.s * qsf, ey = u.c * qsf;
+  const sktrig::SinCosF u = PRE ? q.u : sktrig::sincos_add(mf, l * lk);
+  const float ex = PRE ? q.ex : u.s * qsf, ey = PRE ? q.ey : u.c * qsf;
   bool un, unq = false;
   float mdx = 0.0f, mdy = 0.0f;  // FAST: the move's deltas
   sktrig::SinCos tt{0.0, 1.0};   // the projectile's exact sincos (FAST: on the exact path only)
   sktrig::SinCos tm{0.0, 1.0};   // the move's
-  if constexpr (FAST) {
+  if constexpr (PRE) {
+    mdx = q.mdx;
+    mdy = q.mdy;
+    unq = f && !q.qsafe;
+    un = !q.msafe || unq || (qvalid && !f && tc.qex);
+  } else if constexpr (FAST) {
     const sktrig::FastDelta dm = sktrig::fast_move_delta(tc.m, tc.mok, (float)c.pspeed, clamp_action_f(act.x));
     mdx = dm.x;
     mdy = dm.y;
@@ -1401,7 +1456,7 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
     py = ok ? (int)(ok ? nyf : 0.0) : py;
   } else {  // round_safe: rint(p - d) == p - rintf(d); player_pos_valid's bounds, safe against wrap
     // (selects on the wave-uniform `exact`, no branch: the tick's chain stays one block)
-    const int nx = px - (int)rintf(mdx), ny = py - (int)rintf(mdy);
+    const int nx = px - (PRE ? q.imx : (int)rintf(mdx)), ny = py - (PRE ? q.imy : (int)rintf(mdy));
     const bool ok = (nx >= 0) & (nx <= c.W - c.psize) & (ny >= 0) & (ny <= c.H - c.psize);
     px = exact ? epx : (ok ? nx : px);
     py = exact ? epy : (ok ? ny : py);
@@ -1422,7 +1477,7 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
     if constexpr (FAST) {
       // the step of this tick: a fired projectile's from the angle addition,
       // else the carried one; either way the flight's from here on
-      const int sdx = f ? (int)rintf(ex) : tc.dx, sdy = f ? (int)rintf(ey) : tc.dy;
+      const int sdx = f ? (PRE ? q.iex : (int)rintf(ex)) : tc.dx, sdy = f ? (PRE ? q.iey : (int)rintf(ey)) : tc.dy;
       tc.dx = sdx;
       tc.dy = sdy;
       tc.qex = f ? unq : tc.qex;
@@ -1652,9 +1707,20 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
       __builtin_amdgcn_sched_barrier(0);
       split_carry_advance(tc);  // the last tick's rotation, while this tick's loads fly
       split_carry_pin(tc);
+      // FAST: what the tick computes from the carry and the action alone,
+      // also while the loads fly (about 55 VALU off the chain behind the
+      // wait: 65,536 games 1.59-1.61 against 1.65-1.67 us per tick;
+      // profiles/r12_bench_ab.jsonl).  The action came a tick ahead, so the
+      // wait in front of it is for this wave's previous stores, which the
+      // state loads' own wait implies anyway.
+      SplitPre pre{};
+      if constexpr (FAST) {
+        pre = split_fast_pre(tc.m, tc.mok, cur, c);
+        split_pre_pin(pre);
+      }
       __builtin_amdgcn_sched_barrier(0);
       split_tick_carry<POL, false, true, FAST, true>(a, c, r, L, wc, 0, step0 + (uint64_t)t, w, cur, tc, false, rp,
-                                                     packed, &S);
+                                                     packed, &S, &pre);
       // The wave rests kSteadyRest x 64 cycles between its stores and the
       // next tick's loads of the same lines.  With the loop's shorter tail
       // the reload followed the write-through stores within ~50 instructions
@@ -1663,7 +1729,9 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
       // done / store maze had kept the two apart.  A sleeping wave leaves
       // the issue port to its partner, which filler instructions would not
       // (0: 1.89, 3: 1.77, 4: 1.72, 5: 1.68, 6: 1.66-1.67, 7: 1.65-1.66,
-      // 10: 1.71 us; profiles/r11_steady_rest_sweep.txt).  The fp64-carry
+      // 10: 1.71 us; profiles/r11_steady_rest_sweep.txt; with SplitPre under
+      // the loads 0: 1.81, 3: 1.69, 4: 1.64, 5: 1.60, 6: 1.57, 7: 1.56-1.57,
+      // 8: 1.57-1.58, 10: 1.58-1.59; profiles/r12_rest_sweep.jsonl).  The fp64-carry
       // form (the launches under kFastSplitMinTicks ticks) does not rest: its
       // 20-tick launch reads the parent's figure without, and 3.7 % more with
       // (profiles/r11_bench_ab_norest.jsonl, r11_bench_ab_rest_both.jsonl).
