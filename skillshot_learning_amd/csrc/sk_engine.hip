@@ -47,11 +47,14 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "sk_device.hpp"
 #include "sk_host.hpp"
+#include "sk_range.hpp"
 #include "sk_step.hpp"
+
 
 using namespace sk;
 
@@ -1257,7 +1260,19 @@ __device__ __forceinline__ void split_store_pack(const MultiArgs& a, __amdgpu_bu
 // the exchange format and leaves the loop).  The done / winner rows go
 // through buffer resources at 32-bit offsets (SplitSteady), and the episode
 // counts and the restart sit behind one ballot of `done`: a wave of 32 games
-// has a finished one in about one tick in forty.
+// has a finished one in about one tick in forty.  Its range tests (the
+// move's and the projectile's bounds, the collision's intervals) take one
+// unsigned compare each (sk_range.hpp; the host admits a launch to the steady
+// loop only for a configuration where that form is exact, skrange::cfg_ok).
+//
+// FULL (STEADY only): every lane of the wave is in range, `L.in` is true at
+// compile time: no lane mask around the key check, the fit test, the stores
+// and the done rows.  Every wave of a launch but at most its last.
+//
+// The PACK forms evaluate one collision test per lane, "my player is hit by
+// the partner's projectile", and exchange the bit with one more pair_swap
+// (65,536 games 1.53-1.55 against 1.59-1.60 us per tick; with the one-compare
+// tests 1.46-1.49, with FULL 1.43-1.46; profiles/r13_bench_ab.jsonl).
 struct SplitSteady {
   __amdgpu_buffer_rsrc_t ra, rd, rw;  // the action ring, done, winner (a NULL output: no records, its stores are dropped)
   uint32_t va, vd;                    // this lane's byte offset in an action slab / an output row
@@ -1307,7 +1322,7 @@ __device__ __forceinline__ void split_pre_pin(SplitPre& q) {
   q.msafe = __builtin_amdgcn_inverse_ballot_w64(ms);
   q.qsafe = __builtin_amdgcn_inverse_ballot_w64(qs);
 }
-template <int POL, bool OBS, bool PACK = false, bool FAST = false, bool STEADY = false>
+template <int POL, bool OBS, bool PACK = false, bool FAST = false, bool STEADY = false, bool FULL = false>
 __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& c, __amdgpu_buffer_rsrc_t r,
                                                  SplitLane& L, WaveCtr& wc, int64_t so, uint64_t step,
                                                  const SplitRaw& w, float2 act,
@@ -1318,8 +1333,10 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
   static_assert(!(OBS && PACK), "the full contract never packs");
   static_assert(!(OBS && FAST), "the observation needs the exact sincos");
   static_assert(PACK || !STEADY, "the steady loop is the packed kernel's");
+  static_assert(STEADY || !FULL, "the full-wave form is the steady loop's");
   using sktrig::round_safe;
   const int p = L.p;
+  const bool in = FULL || L.in;
   double rot = __builtin_bit_cast(double, w.rot), qrot = __builtin_bit_cast(double, w.qrot);
   int px = w.pp.x, py = w.pp.y, qx = w.qq.x, qy = w.qq.y, qcd = w.ca.x, qage = w.ca.y, ticks = w.mi.x;
   const unsigned flags = (unsigned)w.mi.y;
@@ -1338,7 +1355,7 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
   const double q_old = qrot;
   const bool f = qcd <= 0;  // fires this tick (Player.py:80)
   const bool miss = (!STEADY && !tc.have) || !same_bits(rot, tc.kr) || (qvalid && !f && !same_bits(qrot, tc.kq));
-  if (__ballot(L.in && miss) != 0) {  // the launch's first tick
+  if (__ballot(in && miss) != 0) {  // the launch's first tick
     if constexpr (FAST) {
       bool kq;
       tc.m = sktrig::sincos_fast(rot, &tc.mok);
@@ -1409,7 +1426,7 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
       }
     }
   }
-  if (__builtin_expect(__ballot(L.in && un) != 0, 0)) {  // the exact sincos of the fired projectiles
+  if (__builtin_expect(__ballot(in && un) != 0, 0)) {  // the exact sincos of the fired projectiles
     if constexpr (FAST) {  // ... and of the move and the projectile in flight
       const double qa = f ? rn : qrot;
       bool k0, k1;
@@ -1457,7 +1474,9 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
   } else {  // round_safe: rint(p - d) == p - rintf(d); player_pos_valid's bounds, safe against wrap
     // (selects on the wave-uniform `exact`, no branch: the tick's chain stays one block)
     const int nx = px - (PRE ? q.imx : (int)rintf(mdx)), ny = py - (PRE ? q.imy : (int)rintf(mdy));
-    const bool ok = (nx >= 0) & (nx <= c.W - c.psize) & (ny >= 0) & (ny <= c.H - c.psize);
+    bool ok;
+    if constexpr (STEADY) ok = skrange::fits_board(nx, ny, c.W - c.psize, c.H - c.psize);
+    else ok = (nx >= 0) & (nx <= c.W - c.psize) & (ny >= 0) & (ny <= c.H - c.psize);
     px = exact ? epx : (ok ? nx : px);
     py = exact ? epy : (ok ? ny : py);
   }
@@ -1490,7 +1509,9 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
       nx = fast ? nxF : nxE;
       ny = fast ? nyF : nyE;
     }
-    const bool ok = (nx + c.qsize <= c.W) & (nx >= 0) & (ny + c.qsize <= c.H) & (ny >= 0);
+    bool ok;
+    if constexpr (STEADY) ok = skrange::fits_board(nx, ny, c.W - c.qsize, c.H - c.qsize);
+    else ok = (nx + c.qsize <= c.W) & (nx >= 0) & (ny + c.qsize <= c.H) & (ny >= 0);
     const bool upd = lv && qvalid;
     qx = (upd && ok) ? nx : qx;
     qy = (upd && ok) ? ny : qy;
@@ -1498,9 +1519,25 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
     qcd -= lv;
     qage += lv;
   }
-  const int opx = pair_swap(px), opy = pair_swap(py);
+  // SkillshotGame.check_collision (:58-94): player 1 tested first
+  int opx = 0, opy = 0;  // the other player's position (the observation's; the collision's in the 88-B forms)
+  if constexpr (!PACK) {
+    opx = pair_swap(px);
+    opy = pair_swap(py);
+  }
   const int oqx = pair_swap(qx), oqy = pair_swap(qy), oqv = pair_swap(qvalid);
-  {  // SkillshotGame.check_collision (:58-94): player 1 tested first
+  if constexpr (PACK) {
+    // the packed forms: one test per lane, "my player is hit by the partner's
+    // projectile", and the pair exchanges the bit (skrange::pair_hit); the
+    // steady tick's test in its one-compare form (sk_range.hpp)
+    bool mine;
+    if constexpr (STEADY) mine = (int)(oqv != 0) & (int)skrange::box_hit(px, py, c.psize, oqx, oqy, c.qsize);
+    else mine = hit_test_s(c, px, py, oqx, oqy, oqv);
+    const bool theirs = pair_swap((int)mine) != 0;
+    const skrange::PairHit h = skrange::pair_hit(lv != 0, p ? theirs : mine, p ? mine : theirs);
+    winner = h.h1 ? 1 : (h.h2 ? 2 : winner);
+    live = ((int)h.h1 | (int)h.h2) ? 0 : live;
+  } else {
     const int p1x = p ? opx : px, p1y = p ? opy : py, q1x = p ? oqx : qx, q1y = p ? oqy : qy, q1v = p ? oqv : qvalid;
     const int p2x = p ? px : opx, p2y = p ? py : opy, q2x = p ? qx : oqx, q2y = p ? qy : oqy, q2v = p ? qvalid : oqv;
     const bool h1 = lv && hit_test_s(c, p1x, p1y, q2x, q2y, q2v);
@@ -1513,26 +1550,26 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
   if constexpr (!STEADY) ctr_settle(wc);
   bool to_pack = false;
   if constexpr (PACK) {
-    const bool fit = !L.in || ((int)pack_fits_player(px, py, qx, qy, qcd, qage, qvalid) &
+    const bool fit = !in || ((int)pack_fits_player(px, py, qx, qy, qcd, qage, qvalid) &
                                (int)pack_fits_game(ticks, live, winner));
     to_pack = (STEADY || !last) && __ballot(!fit) == 0;  // wave-uniform
   }
   if (PACK && to_pack) {  // the packed halves out before done / restart
     const bool qch = (!STEADY && !packed) || __double_as_longlong(qrot) != __double_as_longlong(q_old);
     const unsigned hi = p ? pack_flags(oqv, qvalid, live, winner) : (unsigned)ticks;
-    if (L.in) split_store_pack<POL>(a, rp, L, rot, qrot, qch, pack_pos(px, py, qx, qy), pack_cah(qcd, qage, hi));
+    if (in) split_store_pack<POL>(a, rp, L, rot, qrot, qch, pack_pos(px, py, qx, qy), pack_cah(qcd, qage, hi));
   } else {  // the state out before done / restart (multi_compute's early store, for its reason)
     const unsigned fl = (unsigned)(qvalid & 0xff) | ((unsigned)(oqv & 0xff) << 8) | ((unsigned)(live & 0xff) << 16) |
                         ((unsigned)(winner & 0xff) << 24);
     const bool qch = STEADY || (PACK && packed) || __double_as_longlong(qrot) != __double_as_longlong(q_old);
-    if (L.in) split_store_state<POL>(a, r, L, px, py, rot, qx, qy, qrot, qch, qcd, qage, ticks, fl);
+    if (in) split_store_state<POL>(a, r, L, px, py, rot, qx, qy, qrot, qch, qcd, qage, ticks, fl);
   }
   bool amb = false;
   double gq = 0.0;  // the fast projectile gradient (the ambiguous flag's interval check)
   const int aqx = qx, aqy = qy;  // the post-tick projectile, for the flag's redo
   const double aqrot = qrot;
   if constexpr (OBS) {
-    if (L.in) {  // prepare_states / calculate_rewards_* (SkillshotLearner.py:512-603) of the post-tick state
+    if (in) {  // prepare_states / calculate_rewards_* (SkillshotLearner.py:512-603) of the post-tick state
       float o[12], pd;
       obs12_sc(c, px, py, rot, pr, qx, qy, qrot, tq_obs, qcd, qvalid, opx, opy, o, &pd, &amb, &gq);
       if (a.obs) store_obs(a.obs + so * 24 * a.n, a.n, p, L.i, o);
@@ -1549,8 +1586,8 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
       }
     }
   }
-  const bool d = L.in && ((!live) || (ticks >= a.tick_limit));  // SkillshotLearner.py:302
-  if (L.in && p == 0) {
+  const bool d = in && ((!live) || (ticks >= a.tick_limit));  // SkillshotLearner.py:302
+  if (in && p == 0) {
     if constexpr (STEADY) {
       __builtin_amdgcn_raw_buffer_store_b8((unsigned char)d, ss->rd, ss->vd, ss->dso, 0);
       __builtin_amdgcn_raw_buffer_store_b8((unsigned char)winner, ss->rw, ss->vd, ss->dso, 0);
@@ -1699,7 +1736,8 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
     S.va = (uint32_t)aoff * 8u;
     S.vd = (uint32_t)L.ic;
     S.aso = S.dso = 0;
-    auto steady_tick = [&](const float2& cur, float2& nxt) {
+    const bool full_wave = __ballot(L.in) == ~0ull;  // wave-uniform
+    auto steady_tick = [&](auto full, const float2& cur, float2& nxt) __attribute__((always_inline)) {
       SplitRaw w;
       split_load_pack<POL>(a, rp, L, w);
       const skb2i na = __builtin_amdgcn_raw_buffer_load_b64(S.ra, S.va, S.aso, 2);  // nontemporal, as load_action
@@ -1719,8 +1757,8 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
         split_pre_pin(pre);
       }
       __builtin_amdgcn_sched_barrier(0);
-      split_tick_carry<POL, false, true, FAST, true>(a, c, r, L, wc, 0, step0 + (uint64_t)t, w, cur, tc, false, rp,
-                                                     packed, &S, &pre);
+      split_tick_carry<POL, false, true, FAST, true, decltype(full)::value>(a, c, r, L, wc, 0, step0 + (uint64_t)t, w,
+                                                                            cur, tc, false, rp, packed, &S, &pre);
       // The wave rests kSteadyRest x 64 cycles between its stores and the
       // next tick's loads of the same lines.  With the loop's shorter tail
       // the reload followed the write-through stores within ~50 instructions
@@ -1754,15 +1792,23 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
         // waited for the wave's own state stores to be acknowledged.
         float2 sa0 = pa0, sa1 = pa1;
         asm volatile("" : "+v"(sa1.x), "+v"(sa1.y));
-        do {  // two steady ticks per turn: neither is the launch's last
-          steady_tick(sa1, sa0);
-          ++t;
-          odd = packed;  // (no break out of the middle: its edge shared the latch's block, and the copy came back)
-          if (odd) {
-            steady_tick(sa0, sa1);
+        auto steady_turns = [&](auto full) __attribute__((always_inline)) {
+          do {  // two steady ticks per turn: neither is the launch's last
+            steady_tick(full, sa1, sa0);
             ++t;
-          }
-        } while (packed && t + 2 < a.n_ticks);
+            odd = packed;  // (no break out of the middle: its edge shared the latch's block, and the copy came back)
+            if (odd) {
+              steady_tick(full, sa0, sa1);
+              ++t;
+            }
+          } while (packed && t + 2 < a.n_ticks);
+        };
+        // A wave with all 64 lanes in range (every wave but at most the
+        // launch's last) runs the loop's FULL form, without the lane mask
+        // around the key check, the fit test, the stores and the done rows;
+        // the partial wave keeps the masked steady tick.
+        if (full_wave) steady_turns(std::true_type{});
+        else steady_turns(std::false_type{});
         pa0 = sa0;
         pa1 = sa1;
         asm volatile("" : "+v"(pa0.x), "+v"(pa0.y), "+v"(pa1.x), "+v"(pa1.y));
@@ -2723,7 +2769,11 @@ static int step_multi(sk_env* e, const float* actions, int64_t ring_slabs, int64
   a.ring = ring_slabs;
   a.slab0 = slab0;
   a.n_ticks = n_ticks;
-  a.steady32 = split_steady_fits32(e->n, ring_slabs, out_slabs, out_stride) ? 1 : 0;
+  // (and its integer range tests take their one-compare form: skrange::cfg_ok)
+  a.steady32 = split_steady_fits32(e->n, ring_slabs, out_slabs, out_stride) &&
+                       skrange::cfg_ok(e->dcfg.W, e->dcfg.H, e->dcfg.psize, e->dcfg.qsize, e->dcfg.pspeed, e->dcfg.qspeed)
+                   ? 1
+                   : 0;
   a.done = done;
   a.winner = winner;
   a.out_stride = out_stride;
