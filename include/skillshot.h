@@ -298,6 +298,30 @@ int sk_env_act_match(sk_env* env, const float* actor1_flat, const void* actor1_p
                      const void* actor2_pack, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
                      int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, void* stream);
 
+/* League evaluation in ONE launch (ABI 13, added: a new symbol, nothing
+ * existing changes, so SK_ABI_VERSION stays 13): every ordered pairing of K
+ * actors plays sk_env_act_match's matches side by side.  The env holds
+ * n_pairs * block games, block a multiple of 32; pairing p owns games
+ * p block .. (p + 1) block - 1 and plays them with seat 1 acting from actor
+ * pairs[p][0] and seat 2 from actor pairs[p][1].  nets uint64[n_actors][2]
+ * and pairs int32[n_pairs][2] are DEVICE tables: nets[k] = the device
+ * addresses of actor k's flat fp32 vector and of its split pack
+ * (sk_actor_split_pack_f32, 16-byte aligned).  A pairing that needs fewer
+ * than `block` games is padded with games that are not live (game_live = 0):
+ * they are neither stepped nor written and their lengths are 0.  A pairing
+ * whose actor index lies outside [0, n_actors), or whose actor has a null or
+ * misaligned address, is not played: its games get lengths 0 and nothing
+ * else of theirs is written.  obs2, returns (in/out), lengths, last_half,
+ * n_ticks, reward_kind, tick_limit, the step counter and continuing a match
+ * in a later call: as sk_env_act_match.  SK_EINVAL, before any launch, for a
+ * NULL table, obs2 or lengths, n_ticks <= 0, n_actors < 1, n_pairs < 1,
+ * block <= 0 or block % 32 != 0, an env that does not hold n_pairs * block
+ * games, a misaligned pointer, and the CPU backend.  Stream-ordered and
+ * graph-capturable.  GPU backend only. */
+int sk_env_act_league(sk_env* env, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
+                      int32_t block, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
+                      int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, void* stream);
+
 /* sk_env_act_step prepared, not launched (ABI 8): the same arguments
  * (N % 4 == 0, ring given or not) into *job, and the env advances its step
  * slot as if the launch had been issued.  The job is then run, exactly once

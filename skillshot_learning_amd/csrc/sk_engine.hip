@@ -2677,6 +2677,32 @@ int sk_env_act_match(sk_env* e, const float* actor1_flat, const void* actor1_pac
   return SK_OK;
 }
 
+int sk_env_act_league(sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
+                      int32_t block, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
+                      int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, void* stream) {
+  SK_CHECK_ENV(e);
+  if (!nets || !pairs) return fail(SK_EINVAL, "the nets or the pairs table is NULL");
+  if (!obs2 || !lengths || n_ticks <= 0) return fail(SK_EINVAL, "obs2 or lengths is NULL, or n_ticks <= 0");
+  if (n_actors < 1 || n_pairs < 1) return fail(SK_EINVAL, "n_actors and n_pairs must be at least 1");
+  if (block <= 0 || block % 32) return fail(SK_EINVAL, "block must be a positive multiple of 32");
+  if ((int64_t)e->n != (int64_t)n_pairs * block) return fail(SK_EINVAL, "the env must hold n_pairs * block games");
+  if ((((uintptr_t)nets) & 7) || (((uintptr_t)pairs) & 3))
+    return fail(SK_EINVAL, "nets must be 8-byte aligned, pairs 4-byte");
+  if ((((uintptr_t)lengths) | ((uintptr_t)returns) | ((uintptr_t)last_half)) & 3)
+    return fail(SK_EINVAL, "lengths / returns / last_half must be 4-byte aligned");
+  if (((uintptr_t)obs2) & 15) return fail(SK_EINVAL, "obs2 must be 16-byte aligned");
+  if (e->host) return fail(SK_EINVAL, "sk_env_act_league runs on the GPU backend");
+  StepArgs a;  // (as sk_env_act_match)
+  int rc = act_step_args(e, obs2, nullptr, obs2, returns, reward_kind, nullptr, nullptr, tick_limit, 0, 0, nullptr,
+                         nullptr, 0, nullptr, nullptr, nullptr, a);
+  if (rc != SK_OK) return rc;
+  rc = sk_launch_act_league32(nets, n_actors, pairs, block, a, e->dcfg, obs2, returns, lengths, last_half, n_ticks,
+                              (hipStream_t)stream);
+  if (rc != SK_OK) return fail(rc, "k_act_league32 launch failed");
+  e->parity ^= 1;
+  return SK_OK;
+}
+
 static_assert(sizeof(ActStepJob) <= sizeof(sk_step_job), "sk_step_job too small for ActStepJob");
 
 int sk_env_act_step_job(sk_env* e, const float* actor_flat, const void* actor_pack, const float* acting_obs,

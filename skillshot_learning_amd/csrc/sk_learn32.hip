@@ -2037,6 +2037,98 @@ __global__ void __launch_bounds__(kFwdThreads, SK_EPISODE_WAVES) k_act_match32(c
   if (ret) *ret = acc;
 }
 
+// League evaluation (sk_env_act_league): every ordered pairing of K actors
+// in ONE launch.  The env holds P blocks of `block` games (a multiple of 32),
+// pairing p owns games p block .. (p + 1) block - 1, and workgroup b, which
+// owns games 32b .. 32b + 31 as in k_act_match32, plays pairing b / (block /
+// 32): it reads pairs[p] = (seat-1 actor, seat-2 actor) and those actors'
+// rows of nets = (flat vector, split pack) once, with uniform (scalar)
+// loads, and from there on is k_act_match32's workgroup, the four addresses
+// opaque per tick.  The tick loop is a copy of k_act_match32's, not a shared
+// inlined function: with the body shared, k_act_match32 itself compiled to
+// other code (233 VGPRs and 126 SGPR spills instead of 234 and 140), and the
+// measured kernel stays as it was.  A pairing whose games are no
+// multiple of 32 is padded by the caller with games whose live byte is 0:
+// the loop test never steps or writes them and their lengths stay 0.  A
+// pair index outside [0, K), a null address or one the tile cannot load
+// from (flat 4-byte, pack 16-byte aligned) is not followed: the workgroup
+// writes lengths = 0 for its games, touches nothing else and returns.
+struct LeagueArgs {
+  const uint64_t* nets;  // [K][2]
+  const int32_t* pairs;  // [P][2]
+  int n_actors;
+  int wgs_per_pair;      // block / 32
+};
+__global__ void __launch_bounds__(kFwdThreads, SK_EPISODE_WAVES) k_act_league32(LeagueArgs lg, sk::StepArgs a,
+                                                                                sk::Cfg c, MatchArgs mt) {
+  extern __shared__ __attribute__((aligned(16))) float smem_sl[];
+  const int p = (int)blockIdx.x / lg.wgs_per_pair;
+  const int i1 = lg.pairs[2 * p], i2 = lg.pairs[2 * p + 1];
+  uint64_t f1 = 0, k1 = 0, f2 = 0, k2 = 0;
+  if ((unsigned)i1 < (unsigned)lg.n_actors && (unsigned)i2 < (unsigned)lg.n_actors) {
+    f1 = lg.nets[2 * i1];
+    k1 = lg.nets[2 * i1 + 1];
+    f2 = lg.nets[2 * i2];
+    k2 = lg.nets[2 * i2 + 1];
+  }
+  if (!f1 || !k1 || !f2 || !k2 || ((f1 | f2) & 3) || ((k1 | k2) & 15)) {
+    const int64_t g = (int64_t)blockIdx.x * 32 + threadIdx.x;
+    if (threadIdx.x < 32 && g < a.n) mt.lengths[g] = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && mt.last_half) *mt.last_half = mt.n_ticks & 1;
+    return;
+  }
+  const float* const aflat1 = (const float*)f1;
+  const float* const aflat2 = (const float*)f2;
+  const char* const apack1 = (const char*)k1;
+  const char* const apack2 = (const char*)k2;
+  // ---- k_act_match32's body from here on
+  char* smem = (char*)smem_sl;
+  float2* sAct = (float2*)(smem + kActorTileLds);
+  int* sAlive = (int*)(sAct + 64);
+  const int lane = threadIdx.x & 63;
+  const bool w0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0;
+  const int64_t g0 = (int64_t)blockIdx.x * 32;
+  sk_counters* const slot = nullptr;  // no episode counters (see k_act_episode32)
+  const int64_t n = a.n, gt = 2 * g0 + lane, gi = gt >> 1;  // wave 0: lane -> (game, player)
+  const bool mine = w0 && gi < n;
+  float* const ret = mine && mt.returns ? mt.returns + (int64_t)(lane & 1) * n + gi : nullptr;
+  float acc = ret ? *ret : 0.f;
+  if (mine && (lane & 1) == 0) mt.lengths[gi] = 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0 && mt.last_half) *mt.last_half = mt.n_ticks & 1;
+  for (int t = 0; t < mt.n_ticks; ++t) {
+    // both nets' addresses opaque per tick (k_act_episode32's reason, twice over)
+    const float *af1 = aflat1, *af2 = aflat2;
+    const char *pk1 = apack1, *pk2 = apack2;
+    asm volatile("" : "+s"(af1), "+s"(pk1), "+s"(af2), "+s"(pk2));
+    sk::StepArgs at = a;
+    at.acting_obs = mt.obs2 + (int64_t)(t & 1) * 24 * n;
+    at.obs = mt.obs2 + (int64_t)((t + 1) & 1) * 24 * n;
+    at.reward = mt.returns;
+    sk::StepLane L;
+    if (w0) L = sk::split_load(at, gt, slot);  // lanes past the tail: in = false
+    actor_tile32<false>(net_of(af1, kALd, 2), pk1, at.acting_obs, nullptr, RowsSeat{0, g0, n}, 0.f, 0.f, 0, 0,
+                        actor_lds(smem), sAct);
+    actor_tile32<false>(net_of(af2, kALd, 2), pk2, at.acting_obs, nullptr, RowsSeat{n, g0, n}, 0.f, 0.f, 0, 0,
+                        actor_lds(smem), sAct + 32);
+    if (w0) {
+      // the reference's loop test (:304) on the pre-tick state; both lanes of a game agree
+      const bool alive = L.in && ((L.mi.y >> 16) & 0xff) && L.mi.x < a.tick_limit;
+      L.in = alive;  // an ended game (a pad game from the start) is neither stepped nor written
+      if (alive && L.p == 0) mt.lengths[L.i] = t + 1;
+      const uint64_t any = __ballot(alive);
+      if (lane == 0) *sAlive = any != 0;
+    }
+    __syncthreads();
+    if (!*sAlive) break;  // workgroup-uniform: every game of the workgroup has ended
+    if (w0) {
+      sk::split_finish(at, c, L, sAct[(lane & 1) * 32 + (lane >> 1)], slot);
+      if (L.in && ret) acc += *ret;  // the reward split_finish just stored for this (player, game)
+    }
+    __syncthreads();  // this tick's observations are the next tick's acting rows (this workgroup's own stores)
+  }
+  if (ret) *ret = acc;
+}
+
 // ---------------------------------------------------------------- actor forward, 16-row tiles
 // The same forward for small row counts: a 32-row tile is a serial chain of
 // load latencies around 3.4 us of MFMA per workgroup (9.4 us at 256 rows);
@@ -2452,6 +2544,26 @@ int sk_launch_act_match32(const float* aflat1, const void* apack1, const float* 
   const MatchArgs mt{obs2, returns, lengths, last_half, n_ticks};
   k_act_match32<<<G, kFwdThreads, kActMatchLds, st>>>(aflat1, (const char*)apack1, aflat2, (const char*)apack2, a, c,
                                                       mt);
+  if (hipGetLastError() != hipSuccess) return SK_EHIP;
+  k_episode_finish<<<1, 256, 0, st>>>(lengths, a.n, a.step, nullptr);
+  return hipGetLastError() == hipSuccess ? SK_OK : SK_EHIP;
+}
+
+// every pairing of a league in one launch (sk_env_act_league, csrc/sk_engine.hip): a.n = n_pairs * block,
+// block % 32 == 0; nets / pairs are device tables
+int sk_launch_act_league32(const uint64_t* nets, int n_actors, const int32_t* pairs, int block, const sk::StepArgs& a,
+                           const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
+                           int n_ticks, hipStream_t st) {
+  static bool attr = false;
+  if (!attr) {
+    set_lds32(k_act_league32, kActMatchLds);
+    attr = true;
+  }
+  if (!nets || !pairs || n_actors < 1 || block <= 0 || block % 32 || a.n % block) return SK_EINVAL;
+  const unsigned G = (unsigned)(a.n / 32);
+  const MatchArgs mt{obs2, returns, lengths, last_half, n_ticks};
+  const LeagueArgs lg{nets, pairs, n_actors, block / 32};
+  k_act_league32<<<G, kFwdThreads, kActMatchLds, st>>>(lg, a, c, mt);
   if (hipGetLastError() != hipSuccess) return SK_EHIP;
   k_episode_finish<<<1, 256, 0, st>>>(lengths, a.n, a.step, nullptr);
   return hipGetLastError() == hipSuccess ? SK_OK : SK_EHIP;

@@ -510,3 +510,7 @@ int sk_launch_act_episode32(const float* aflat, const void* apack, float sd, flo
 int sk_launch_act_match32(const float* aflat1, const void* apack1, const float* aflat2, const void* apack2,
                           const sk::StepArgs& a, const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths,
                           int32_t* last_half, int n_ticks, hipStream_t st);
+// k_act_league32 (csrc/sk_learn32.hip): every pairing of K actors, whole matches, one launch
+int sk_launch_act_league32(const uint64_t* nets, int n_actors, const int32_t* pairs, int block, const sk::StepArgs& a,
+                           const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
+                           int n_ticks, hipStream_t st);

@@ -845,6 +845,38 @@ def _match_summary(games, wins, losses, draws, ticks_sum, ret_self, ret_opp, sea
     return d
 
 
+def bradley_terry_elo(score, n):
+    """Elo ratings of K actors from their pairwise results, by the maximum
+    likelihood fit of the Bradley-Terry model P(i beats j) = p_i / (p_i +
+    p_j).  score[i][j]: what i scored against j (a win 1, a draw 1/2), n[i][j]
+    = n[j][i]: the games the two played; float arrays [K, K], the diagonals
+    ignored.  One virtual game per pair, drawn 1/2 - 1/2, is added, so an
+    actor that never lost (or never scored) keeps a finite rating.  The MM
+    iteration p_i <- S_i / sum_{j != i} n_ij / (p_i + p_j), S_i = sum_j
+    score_ij (Hunter 2004), renormalised to geometric mean 1, runs until the
+    largest relative change is below 1e-12 or for 1,000 iterations.  Returns
+    elo = 400 log10 p, float64 [K], mean 0."""
+    s = np.array(score, dtype=np.float64)
+    m = np.array(n, dtype=np.float64)
+    if s.ndim != 2 or s.shape[0] != s.shape[1] or m.shape != s.shape or s.shape[0] < 2:
+        raise ValueError("score and n must be [K, K] arrays, K >= 2")
+    if (s < 0).any() or (m < 0).any() or not np.allclose(m, m.T):
+        raise ValueError("score and n must be non-negative and n symmetric")
+    off = ~np.eye(s.shape[0], dtype=bool)
+    s = np.where(off, s + 0.5, 0.0)
+    m = np.where(off, m + 1.0, 0.0)
+    S = s.sum(1)
+    p = np.ones(s.shape[0])
+    for _ in range(1000):
+        q = S / (m / (p[:, None] + p[None, :])).sum(1)
+        q /= np.exp(np.log(q).mean())
+        change = np.max(np.abs(q - p) / p)
+        p = q
+        if change < 1e-12:
+            break
+    return 400.0 * np.log10(p)
+
+
 class SkillshotLearner:
     """Batched self-play DDPG learner (SkillshotLearner.py:13-682 API shape).
 
@@ -1142,9 +1174,7 @@ class SkillshotLearner:
         limit = int(self.model_param_game_tick_limit if tick_limit is None else tick_limit)
         g = self._eval_env(n, limit, seed)
         mine, theirs = self._match_actors(opponent)
-        use_kernel = (self.precision == "fp32" and self.device.type == "cuda" and
-                      getattr(self.actor_kernel, "fused_act_step", False) and
-                      os.environ.get("SK_MATCH_KERNEL", "1") != "0")
+        use_kernel = self._match_kernel_usable() and os.environ.get("SK_MATCH_KERNEL", "1") != "0"
         g.step_counter = 0
         g.reset(random_positions=self.use_random_start)
         start = g.state_dict() if swap_sides else None
@@ -1153,22 +1183,134 @@ class SkillshotLearner:
             if seat == 2:
                 g.load_state_dict(start)
             a1, a2 = (mine, theirs) if seat == 1 else (theirs, mine)
-            obs, _ = g.observe(reward=reward)
-            if use_kernel:
-                m = g.act_match(a1[1], a2[1], obs, n_ticks=limit, reward=reward,
-                                out=getattr(g, "_match_bufs", None))
-                g._match_bufs = m
-                ret, winner, ticks = m["returns"], g.winner_id, g.ticks
-            else:
-                ret, winner, ticks = self._match_loop(g, a1[0], a2[0], obs, reward)
-            o = match_outcomes(winner, seat)
-            rows.append(torch.stack([v.double() for v in (o["wins"], o["losses"], o["draws"], ticks.sum(),
-                                                          ret[seat - 1].sum(), ret[2 - seat].sum())]))
+            rows.append(self._match_leg(g, a1, a2, seat, limit, reward, use_kernel))
         flat = torch.stack(rows).cpu()  # the one host read: six scalars per leg
         legs = [_match_summary(n, *flat[k].tolist(), seat=k + 1) for k in range(len(rows))]
         total = _match_summary(n * len(rows), *flat.sum(0).tolist())
         total["legs"] = legs
         return total
+
+    def league(self, actors, games=None, tick_limit=None, reward="looking", seed=None):
+        """Round robin of K actors: every ORDERED pairing (i, j), i != j,
+        plays `games` whole games, i in seat 1 and j in seat 2, all from
+        evaluate's start states (the same `games`, tick_limit and seed give
+        the games evaluate plays, so entry [i][j] is the leg evaluate would
+        play with i in seat 1 against j).
+
+        actors  a sequence of 2 to 32 entries of the kinds evaluate takes as
+                `opponent`; None is the learner's current actor.  The nets
+                built for them are held until the next league call (a holder
+                of league's own, not evaluate's 8-entry cache).
+        games   games per ordered pairing (default n_envs)
+
+        With the fp32 acting kernel on a GPU all K (K - 1) pairings play in
+        ONE launch (VecSkillshotGame.act_league) on a league env of K (K - 1)
+        blocks of 32 ceil(games / 32) games, cached per (pairings, block, tick
+        limit, seed) and refilled at every call from the evaluation env's
+        reset: each block holds the `games` start states, then pad games that
+        are not live.  The tallies are reduced on the device and read once.
+        Otherwise, or with SK_LEAGUE_KERNEL=0, the pairings play one by one
+        with evaluate's leg.  Nothing of training moves (evaluate's promise).
+
+        Returns a dict.  Ordered tables, nested lists [K][K], row = seat 1,
+        column = seat 2, diagonal 0: seat_wins (player 2 was hit), seat_losses
+        (player 1 was hit), seat_draws, mean_ticks, mean_return (seat 1's) and
+        opponent_mean_return (seat 2's).  Derived on the host: wins[i][j] =
+        seat_wins[i][j] + seat_losses[j][i] (i's wins over j from both seats),
+        draws[i][j] = seat_draws[i][j] + seat_draws[j][i], score[i] = (wins +
+        draws / 2) over the 2 (K - 1) games i played, elo
+        (bradley_terry_elo of the pairwise scores) and ranking (actor indices,
+        best elo first, ties by index); plus games and n_actors."""
+        try:
+            entries = list(actors)
+        except TypeError:
+            raise TypeError("actors must be a sequence of 2 to 32 actors")
+        K = len(entries)
+        if not 2 <= K <= 32:
+            raise ValueError("league needs 2 to 32 actors")
+        n = int(self.n_envs if games is None else games)
+        limit = int(self.model_param_game_tick_limit if tick_limit is None else tick_limit)
+        used = {}
+        players = [self._match_actor(e, cache=self.__dict__.setdefault("_league_actors", {}), used=used)
+                   for e in entries]
+        self._league_actors = used  # this call's nets stay, earlier leagues' go
+        pairs = [(i, j) for i in range(K) for j in range(K) if i != j]
+        g = self._eval_env(n, limit, seed)
+        g.step_counter = 0
+        g.reset(random_positions=self.use_random_start)
+        use_kernel = (self._match_kernel_usable() and all(p[1] is not None for p in players) and
+                      os.environ.get("SK_LEAGUE_KERNEL", "1") != "0")
+        if use_kernel:
+            rows = self._league_launch(g, [p[1] for p in players], pairs, n, limit, reward)
+        else:
+            start = g.state_dict()
+            legs = []
+            for k, (i, j) in enumerate(pairs):
+                if k:
+                    g.load_state_dict(start)
+                legs.append(self._match_leg(g, players[i], players[j], 1, limit, reward,
+                                            self._match_kernel_usable() and players[i][1] is not None and
+                                            players[j][1] is not None and
+                                            os.environ.get("SK_MATCH_KERNEL", "1") != "0"))
+            rows = torch.stack(legs)
+        flat = rows.cpu().numpy()  # the one host read: six scalars per pairing
+        tab = np.zeros((6, K, K))
+        for k, (i, j) in enumerate(pairs):
+            tab[:, i, j] = flat[k]
+        sw, sl, sd = tab[0], tab[1], tab[2]
+        wins, draws = sw + sl.T, sd + sd.T
+        played = np.where(np.eye(K, dtype=bool), 0.0, 2.0 * n)
+        score = (wins + 0.5 * draws).sum(1) / played.sum(1)
+        elo = bradley_terry_elo(wins + 0.5 * draws, played)
+
+        def ints(a):
+            return [[int(v) for v in r] for r in a]
+
+        return dict(n_actors=K, games=n, seat_wins=ints(sw), seat_losses=ints(sl), seat_draws=ints(sd),
+                    mean_ticks=(tab[3] / n).tolist(), mean_return=(tab[4] / n).tolist(),
+                    opponent_mean_return=(tab[5] / n).tolist(), wins=ints(wins), draws=ints(draws),
+                    score=score.tolist(), elo=elo.tolist(),
+                    ranking=sorted(range(K), key=lambda i: (-elo[i], i)))
+
+    def _league_launch(self, g, kernels, pairs, games, limit, reward):
+        """league's pairings in one launch from env g's current (start) state:
+        fp64 [P, 6] on the device, _match_leg's tallies for seat 1 of every
+        pairing.  The reward sums are taken as _match_leg takes them, an fp32
+        sum over a [2, games] buffer per pairing, so both paths of league
+        return the same numbers."""
+        from .vec_env import PLANES, VecSkillshotGame
+        P, block = len(pairs), 32 * ((games + 31) // 32)
+        envs = self.__dict__.setdefault("_league_envs", {})
+        key = (P, block, limit, g.seed)
+        lg = envs.get(key)
+        if lg is None:
+            lg = envs[key] = VecSkillshotGame(P * block, device=self.device, seed=g.seed, env_offset=g.env_offset,
+                                              tick_limit=limit, random_positions=self.use_random_start)
+            lg._league_obs = torch.zeros((2, P, block, 12), dtype=torch.float32, device=self.device)
+        if getattr(lg, "_league_ret", None) is None or lg._league_ret.shape[1] != games:
+            lg._league_ret = torch.empty((2, games), dtype=torch.float32, device=self.device)
+        lg.step_counter = 0
+        for name, _, w in PLANES:  # every block: the start states, then pad games (game 0's state, not live)
+            src, dst = getattr(g, name), getattr(lg, name).view(P, block, w)
+            dst[:, :games] = src[None]
+            dst[:, games:] = src[0]
+        lg.misc.view(P, block, 2)[:, games:, 1] &= ~0x00FF0000
+        obs, _ = g.observe(reward=reward)
+        lg._league_obs[:, :, :games] = obs[:, None]
+        m = lg.act_league(kernels, pairs, block, lg._league_obs, n_ticks=limit, reward=reward,
+                          out=getattr(lg, "_league_bufs", None))
+        lg._league_bufs = m
+        w = lg.winner_id.view(P, block)[:, :games]
+        ticks = lg.ticks.view(P, block)[:, :games]
+        ret, buf = m["returns"].view(2, P, block), lg._league_ret
+        sums = []
+        for p in range(P):
+            buf.copy_(ret[:, p, :games])
+            sums.append(buf[0].sum())
+            sums.append(buf[1].sum())
+        sums = torch.stack(sums).view(P, 2).double()
+        return torch.stack([(w == 2).sum(1).double(), (w == 1).sum(1).double(), (w == 0).sum(1).double(),
+                            ticks.sum(1).double(), sums[:, 0], sums[:, 1]], 1)
 
     def _eval_env(self, games, tick_limit, seed):
         from .vec_env import VecSkillshotGame
@@ -1181,23 +1323,56 @@ class SkillshotLearner:
                                          tick_limit=tick_limit, random_positions=self.use_random_start)
         return envs[key]
 
+    def _match_kernel_usable(self):
+        """the one-launch match kernels play this learner's actors: the fp32
+        acting kernel on a GPU"""
+        return (self.precision == "fp32" and self.device.type == "cuda" and
+                getattr(self.actor_kernel, "fused_act_step", False))
+
+    def _match_leg(self, g, a1, a2, seat, limit, reward, use_kernel):
+        """one leg on env g from its current state, seat 1 acting from a1 and
+        seat 2 from a2 (each a pair of _match_actors): six 0-d fp64 tallies on
+        the device, from the point of view of the player in `seat` — wins,
+        losses, draws, the games' ticks, the own and the other seat's reward
+        sums (fp32 sums over the games)"""
+        obs, _ = g.observe(reward=reward)
+        if use_kernel:
+            m = g.act_match(a1[1], a2[1], obs, n_ticks=limit, reward=reward,
+                            out=getattr(g, "_match_bufs", None))
+            g._match_bufs = m
+            ret, winner, ticks = m["returns"], g.winner_id, g.ticks
+        else:
+            ret, winner, ticks = self._match_loop(g, a1[0], a2[0], obs, reward)
+        o = match_outcomes(winner, seat)
+        return torch.stack([v.double() for v in (o["wins"], o["losses"], o["draws"], ticks.sum(),
+                                                 ret[seat - 1].sum(), ret[2 - seat].sum())])
+
     def _match_actors(self, opponent):
         """(callable obs [M, 12] -> actions [M, 2], ActorKernel32 or None) of
         the learner and of the opponent; an opponent's net and kernel are
         built once per opponent object and kept"""
+        mine = self._match_actor(None)
+        return mine, (mine if opponent is None else self._match_actor(opponent))
+
+    def _match_actor(self, opponent, cache=None, used=None):
+        """_match_actors' pair for one actor (None: the learner's own).  The
+        nets built for opponents are kept in `cache` (default: evaluate's, at
+        most 8 entries, the oldest dropped first); `used`, a dict, receives
+        the entry this call went through."""
         def pair(module, kernel):
             if kernel is not None:
                 return (lambda x: kernel(x)), (kernel if getattr(kernel, "fused_act_step", False) else None)
             return (lambda x: module(x)), None
 
-        mine = pair(self.model_actor, self.actor_kernel)
         if opponent is None:
-            return mine, mine
+            return pair(self.model_actor, self.actor_kernel)
         if isinstance(opponent, SkillshotLearner):
             if opponent.device == self.device and type(opponent.actor_kernel) is type(self.actor_kernel):
-                return mine, pair(opponent.model_actor, opponent.actor_kernel)
+                return pair(opponent.model_actor, opponent.actor_kernel)
             opponent = opponent.model_actor
-        cache = self.__dict__.setdefault("_eval_opponents", {})
+        bounded = cache is None
+        if bounded:
+            cache = self.__dict__.setdefault("_eval_opponents", {})
         if isinstance(opponent, bool) or not isinstance(opponent, (int, np.integer, dict, nn.Module)):
             raise TypeError("opponent: None, an Actor, an actor state_dict, a SkillshotLearner or a checkpoint index")
         if isinstance(opponent, (int, np.integer)):
@@ -1211,9 +1386,11 @@ class SkillshotLearner:
             with torch.random.fork_rng(devices=[]):  # Actor() draws its initial weights
                 net = Actor().to(self.device)
             kernel = type(self.actor_kernel)(net, seed=0) if self.actor_kernel is not None else None
-            while len(cache) >= 8:  # (state_dicts made afresh per call would pile up)
+            while bounded and len(cache) >= 8:  # (state_dicts made afresh per call would pile up)
                 cache.pop(next(iter(cache)))
             ent = cache[key] = dict(source=opponent, net=net, kernel=kernel)
+        if used is not None:
+            used[key] = ent
         net = ent["net"]
         with torch.no_grad():  # the weights are copied at every call: the opponent may have trained since
             if isinstance(opponent, (int, np.integer)):
@@ -1226,7 +1403,7 @@ class SkillshotLearner:
                 net.load_state_dict({k: v.to(self.device) for k, v in opponent.state_dict().items()})
         if getattr(ent["kernel"], "buf", None) is not None:
             ent["kernel"].refresh()  # the bf16 forward pack does not follow its module
-        return mine, pair(net, ent["kernel"])
+        return pair(net, ent["kernel"])
 
     @torch.no_grad()
     def _match_loop(self, g, act1, act2, obs, reward):

@@ -521,6 +521,78 @@ class VecSkillshotGame:
         return dict(lengths=total, returns=ret, obs=obs, obs2=obs2, call_lengths=call_ln,
                     last_half=o.get("last_half"))
 
+    def act_league(self, actors, pairs, block, start_obs, n_ticks=None, reward="looking", out=None, resume=False):
+        """Every pairing of a league in ONE launch (sk_env_act_league):
+        the env holds len(pairs) blocks of `block` games (a multiple of 32),
+        and the games of block p play act_match's match with seat 1 acting
+        from actors[pairs[p][0]] and seat 2 from actors[pairs[p][1]] (`actors`
+        a list of ActorKernel32, `pairs` a host list of (i, j)).  A pairing
+        that needs fewer than `block` games is padded by the caller with games
+        that are not live: they are not stepped and their lengths are 0.
+        start_obs, n_ticks, reward, resume, the step counter and the returned
+        dict: act_match's.  The two device tables (the actors' addresses, the
+        pairs) are kept in the returned dict (`nets`, `pairs`) and uploaded
+        again only when the actors' buffers or `pairs` differ from the call
+        that made them, so a repeated or captured call with out= allocates
+        and uploads nothing."""
+        if self.is_cpu:
+            raise SkillshotError("act_league runs on the GPU backend (SkillshotLearner.league loops on the CPU one)")
+        actors = list(actors)
+        block = int(block)
+        try:
+            plist = tuple((int(i), int(j)) for i, j in pairs)
+        except (TypeError, ValueError):
+            raise ValueError("pairs must be a list of (seat-1 actor, seat-2 actor) index pairs")
+        if not actors or not plist:
+            raise ValueError("act_league needs at least one actor and one pairing")
+        if not all(hasattr(a, "flat") and hasattr(a, "ensure_pack") for a in actors):
+            raise TypeError("actors must be ActorKernel32 objects (the fp32 actor with its split pack)")
+        if block <= 0 or block % 32:
+            raise ValueError("block must be a positive multiple of 32")
+        if len(plist) * block != self.n:
+            raise ValueError(f"the env holds {self.n} games, not len(pairs) * block = {len(plist) * block}")
+        for i, j in plist:
+            if not (0 <= i < len(actors) and 0 <= j < len(actors)):
+                raise ValueError(f"pair ({i}, {j}) names an actor outside [0, {len(actors)})")
+        T = int(self.tick_limit if n_ticks is None else n_ticks)
+        o = out or {}
+        if resume and (o.get("returns") is None or o.get("lengths") is None):
+            raise ValueError("resume needs the dict a previous act_league returned as out")
+
+        def buf(key, shape, dtype):
+            t = o.get(key)
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=self.device)
+            elif tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"out[{key!r}] must be contiguous {dtype} {shape} on {self.device}")
+            return t
+
+        addr = tuple((a.flat.data_ptr(), a.ensure_pack().data_ptr()) for a in actors)
+        nets = buf("nets", (len(actors), 2), torch.int64)
+        prs = buf("pairs", (len(plist), 2), torch.int32)
+        if o.get("tables") != (addr, plist) or nets is not o.get("nets") or prs is not o.get("pairs"):
+            nets.copy_(torch.tensor(addr, dtype=torch.int64))
+            prs.copy_(torch.tensor(plist, dtype=torch.int32))
+        start = start_obs.reshape(2, self.n, 12)  # (may be out["obs"]: read before it is rewritten)
+        obs2 = buf("obs2", (2, 2, self.n, 12), torch.float32)
+        ret = buf("returns", (2, self.n), torch.float32)
+        call_ln = buf("call_lengths", (self.n,), torch.int32)
+        total = buf("lengths", (self.n,), torch.int32)
+        obs = buf("obs", (2, self.n, 12), torch.float32)
+        obs2[0].copy_(start)
+        if not resume:
+            ret.zero_()
+        check(self._L.sk_env_act_league(self._h, _ptr(nets), len(actors), _ptr(prs), len(plist), block, _ptr(obs2),
+                                        _ptr(ret), _ptr(call_ln), _ptr(o.get("last_half")), T,
+                                        REWARD_KINDS[reward], self.tick_limit, self._stream()))
+        torch.where((call_ln & 1).bool()[None, :, None], obs2[1], obs2[0], out=obs)
+        if resume:
+            total += call_ln
+        else:
+            total.copy_(call_ln)
+        return dict(lengths=total, returns=ret, obs=obs, obs2=obs2, call_lengths=call_ln,
+                    last_half=o.get("last_half"), nets=nets, pairs=prs, tables=(addr, plist))
+
     def step_raw(self, actions_ptr, done_ptr=None, obs_ptr=None, reward_ptr=None, winner_ptr=None,
                  auto_reset=True, stream=None):
         """Pointer-level fused step (bench / graph capture; no allocation)."""
