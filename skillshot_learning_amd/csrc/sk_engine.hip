@@ -514,7 +514,7 @@ struct MultiArgs {
   int64_t ring;           // slabs in the ring
   int64_t slab0;          // slab of tick 0 (< ring)
   int n_ticks;
-  int steady32;           // the packed split kernel's steady loop may run (split_steady_fits32); in n_ticks' padding
+  int steady32;           // the packed split kernel's steady loop may run (step_multi); in n_ticks' padding
   uint8_t* done;          // tick t writes done + t * out_stride (nullable)
   uint8_t* winner;        // same (nullable)
   int64_t out_stride;
@@ -574,14 +574,9 @@ __device__ __forceinline__ void store_env_port(const MultiArgs& a, __amdgpu_buff
   }
 }
 
-// ---- the packed form
-__device__ __forceinline__ bool pack_fits_player(int px, int py, int qx, int qy, int cd, int age, int qv) {
-  return ((unsigned)px < 256u) & ((unsigned)py < 256u) & ((unsigned)qx < 256u) & ((unsigned)qy < 256u) &
-         (cd >= -128) & (cd <= 127) & ((unsigned)age < 256u) & ((unsigned)qv < 2u);
-}
-__device__ __forceinline__ bool pack_fits_game(int ticks, int live, int winner) {
-  return ((unsigned)ticks < 65536u) & ((unsigned)live < 2u) & ((unsigned)winner < 4u);
-}
+// ---- the packed form (its range tests: sk_range.hpp, host-compilable)
+using skrange::pack_fits_game;
+using skrange::pack_fits_player;
 __device__ __forceinline__ unsigned pack_flags(int qv0, int qv1, int live, int winner) {
   return (unsigned)qv0 | ((unsigned)qv1 << 1) | ((unsigned)live << 2) | ((unsigned)winner << 3);
 }
@@ -1255,9 +1250,10 @@ __device__ __forceinline__ void split_store_pack(const MultiArgs& a, __amdgpu_bu
 //
 // STEADY (PACK only): the tick of the packed kernel's steady loop
 // (k_step_split_multi).  Known at compile time: the state arrives packed,
-// the tick is not the launch's last, the carry is valid.  What is left of the
-// form tests is the wave's one `fit` ballot (a wave that stops fitting stores
-// the exchange format and leaves the loop).  The done / winner rows go
+// the tick is not the launch's last, the carry is valid, and the state leaves
+// packed: the generic tick admitted the wave for the rest of the launch
+// (skrange::admit_*: no state of it can stop fitting), so the steady tick has
+// no fit test and no exchange-format stores.  The done / winner rows go
 // through buffer resources at 32-bit offsets (SplitSteady), and the episode
 // counts and the restart sit behind one ballot of `done`: a wave of 32 games
 // has a finished one in about one tick in forty.  Its range tests (the
@@ -1266,7 +1262,7 @@ __device__ __forceinline__ void split_store_pack(const MultiArgs& a, __amdgpu_bu
 // loop only for a configuration where that form is exact, skrange::cfg_ok).
 //
 // FULL (STEADY only): every lane of the wave is in range, `L.in` is true at
-// compile time: no lane mask around the key check, the fit test, the stores
+// compile time: no lane mask around the key check, the stores
 // and the done rows.  Every wave of a launch but at most its last.
 //
 // The PACK forms evaluate one collision test per lane, "my player is hit by
@@ -1328,7 +1324,8 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
                                                  const SplitRaw& w, float2 act,
                                                  typename SplitCarrySel<FAST>::type& tc, bool last,
                                                  __amdgpu_buffer_rsrc_t rp, bool& packed,
-                                                 const SplitSteady* ss = nullptr, SplitPre* pre = nullptr) {
+                                                 const SplitSteady* ss = nullptr, SplitPre* pre = nullptr,
+                                                 int left = 0, bool* admit = nullptr) {
   constexpr bool PRE = FAST && STEADY;  // the state-independent part arrives evaluated (SplitPre)
   static_assert(!(OBS && PACK), "the full contract never packs");
   static_assert(!(OBS && FAST), "the observation needs the exact sincos");
@@ -1548,11 +1545,16 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
   // every load of this tick consumed (see multi_tick); a steady tick is never
   // the launch's last, and the generic tick that is settles the slot
   if constexpr (!STEADY) ctr_settle(wc);
-  bool to_pack = false;
-  if constexpr (PACK) {
+  bool to_pack = STEADY;  // (a steady tick's wave was admitted for the launch: no fit test)
+  if constexpr (PACK && !STEADY) {
     const bool fit = !in || ((int)pack_fits_player(px, py, qx, qy, qcd, qage, qvalid) &
                                (int)pack_fits_game(ticks, live, winner));
-    to_pack = (STEADY || !last) && __ballot(!fit) == 0;  // wave-uniform
+    to_pack = !last && __ballot(!fit) == 0;  // wave-uniform
+    // admission to the steady loop for the `left` ticks after this one
+    // (skrange::admit_*): no lane's state can stop fitting before they end
+    const bool adm = !in || ((int)skrange::admit_player(px, py, qx, qy, qcd, qage, qvalid) &
+                               (int)skrange::admit_game(ticks, live, winner, left));
+    *admit = to_pack && __ballot(!adm) == 0;
   }
   if (PACK && to_pack) {  // the packed halves out before done / restart
     const bool qch = (!STEADY && !packed) || __double_as_longlong(qrot) != __double_as_longlong(q_old);
@@ -1687,6 +1689,7 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
   step_advance(a.step, step0, (uint64_t)a.n_ticks);
   const __amdgpu_buffer_rsrc_t r = raw_rsrc(a.base), rp = PACK ? raw_rsrc(a.pack) : r;
   bool packed = false;  // every launch starts from (and ends in) the exchange format
+  bool admitted = false;  // PACK: the wave stays in the packed form for the rest of the launch (skrange::admit_*)
   int64_t slab = a.slab0, so = a.out0;
   // the slab one tick ahead in the register pair this tick does not read,
   // two ticks per iteration (k_step_multi's action pipeline)
@@ -1709,8 +1712,12 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
     // VALU, 9 of them fp64, against 89 and 50)
     if (tc.pend) split_carry_advance(tc);
     __builtin_amdgcn_sched_barrier(0);
-    split_tick_carry<POL, OBS, PACK, FAST>(a, c, r, L, wc, so, step0 + (uint64_t)t, w, cur, tc, t + 1 == a.n_ticks,
-                                           rp, packed);
+    if constexpr (PACK)
+      split_tick_carry<POL, OBS, PACK, FAST>(a, c, r, L, wc, so, step0 + (uint64_t)t, w, cur, tc, t + 1 == a.n_ticks,
+                                             rp, packed, nullptr, nullptr, a.n_ticks - 1 - t, &admitted);
+    else
+      split_tick_carry<POL, OBS, PACK, FAST>(a, c, r, L, wc, so, step0 + (uint64_t)t, w, cur, tc, t + 1 == a.n_ticks,
+                                             rp, packed);
     slab = slab + 1 == a.ring ? 0 : slab + 1;
     pslab = pslab + 1 == a.ring ? 0 : pslab + 1;
     so = so + 1 == a.out_slabs ? 0 : so + 1;
@@ -1718,12 +1725,16 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
   if constexpr (PACK) {
     // The launch peeled: tick 0 (exchange format in) and the last tick
     // (exchange format out) run the generic tick above; between them, while
-    // the wave fits the packed form, the steady loop: packed in and out, not
-    // the last tick, the carry pending (split_tick_carry's STEADY form), the
-    // ring and the output rows at 32-bit byte offsets (a.steady32: the host
-    // checked that they fit) with one scalar add and compare each per tick.
-    // A wave whose ballot fails leaves for the generic tick and comes back
-    // at the next odd tick at which it is packed again.
+    // for a wave admitted for the rest of the launch, the steady loop: packed
+    // in and out, not the last tick, the carry pending (split_tick_carry's
+    // STEADY form), the ring and the output rows at 32-bit byte offsets
+    // (a.steady32: the host checked that they fit) with one scalar add and
+    // compare each per tick.  Admission (skrange::admit_*, balloted in the
+    // generic tick on its post-tick state): no state of the wave can stop
+    // fitting the packed form in the ticks that remain, so the loop is a
+    // plain tick count with no fit test and no way out.  A wave that is not
+    // admitted runs the generic tick, which still packs per tick while the
+    // state fits, and asks again after every even tick.
     SplitSteady S;
     const uint32_t slab_b = (uint32_t)a.n * 16u, ring_b = (uint32_t)a.ring * slab_b;
     const uint32_t out_b = (uint32_t)a.out_slabs * (uint32_t)a.out_stride;
@@ -1780,8 +1791,7 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
     do {  // n_ticks >= 1 (host-checked); t is even here and this tick's actions are in pa0
       one_tick(pa0, pa1);
       if (++t >= a.n_ticks) break;
-      bool odd = true;
-      if (a.steady32 && packed && t + 2 < a.n_ticks) {
+      if (a.steady32 && admitted && t + 2 < a.n_ticks) {
         const int t_in = t;
         const uint32_t slab_in = (uint32_t)slab, so_in = (uint32_t)so;
         S.aso = (uint32_t)pslab * slab_b;
@@ -1793,19 +1803,16 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
         float2 sa0 = pa0, sa1 = pa1;
         asm volatile("" : "+v"(sa1.x), "+v"(sa1.y));
         auto steady_turns = [&](auto full) __attribute__((always_inline)) {
-          do {  // two steady ticks per turn: neither is the launch's last
+          do {  // two steady ticks per turn: neither is the launch's last; a plain tick count
             steady_tick(full, sa1, sa0);
+            ++t;  // (the tick's RNG step counts from t)
+            steady_tick(full, sa0, sa1);
             ++t;
-            odd = packed;  // (no break out of the middle: its edge shared the latch's block, and the copy came back)
-            if (odd) {
-              steady_tick(full, sa0, sa1);
-              ++t;
-            }
-          } while (packed && t + 2 < a.n_ticks);
+          } while (t + 2 < a.n_ticks);
         };
         // A wave with all 64 lanes in range (every wave but at most the
         // launch's last) runs the loop's FULL form, without the lane mask
-        // around the key check, the fit test, the stores and the done rows;
+        // around the key check, the stores and the done rows;
         // the partial wave keeps the masked steady tick.
         if (full_wave) steady_turns(std::true_type{});
         else steady_turns(std::false_type{});
@@ -1818,11 +1825,8 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
         pslab = slab + 1 == a.ring ? 0 : slab + 1;
         so = (int64_t)((so_in + dt) % (uint32_t)a.out_slabs);
       }
-      if (odd) {
-        one_tick(pa1, pa0);
-        ++t;
-      }
-    } while (t < a.n_ticks);
+      one_tick(pa1, pa0);
+    } while (++t < a.n_ticks);
   } else {
     do {  // n_ticks >= 1 (host-checked)
       one_tick(pa0, pa1);
@@ -2795,9 +2799,13 @@ static int step_multi(sk_env* e, const float* actions, int64_t ring_slabs, int64
   a.ring = ring_slabs;
   a.slab0 = slab0;
   a.n_ticks = n_ticks;
-  // (and its integer range tests take their one-compare form: skrange::cfg_ok)
+  // (and its integer range tests take their one-compare form: skrange::cfg_ok;
+  // a wave stays in it for the rest of the launch: skrange::admit_cfg, with
+  // the restart positions in a byte, which the packed kernel needs anyway:
+  // restart_fits below)
   a.steady32 = split_steady_fits32(e->n, ring_slabs, out_slabs, out_stride) &&
-                       skrange::cfg_ok(e->dcfg.W, e->dcfg.H, e->dcfg.psize, e->dcfg.qsize, e->dcfg.pspeed, e->dcfg.qspeed)
+                       skrange::cfg_ok(e->dcfg.W, e->dcfg.H, e->dcfg.psize, e->dcfg.qsize, e->dcfg.pspeed, e->dcfg.qspeed) &&
+                       skrange::admit_cfg(e->dcfg.W, e->dcfg.H, e->dcfg.psize, e->dcfg.qsize, e->dcfg.cdmax)
                    ? 1
                    : 0;
   a.done = done;

@@ -64,4 +64,46 @@ SKR_HD PairHit pair_hit(bool lv, bool hit_p1, bool hit_p2) {
   return r;
 }
 
+// ---- the packed form's ranges (pack_pos / pack_cah, sk_engine.hip): a byte
+// per coordinate, a signed byte of cooldown, a byte of age, 16 bits of ticks
+SKR_HD bool pack_fits_player(int px, int py, int qx, int qy, int cd, int age, int qv) {
+  return ((unsigned)px < 256u) & ((unsigned)py < 256u) & ((unsigned)qx < 256u) & ((unsigned)qy < 256u) &
+         (cd >= -128) & (cd <= 127) & ((unsigned)age < 256u) & ((unsigned)qv < 2u);
+}
+SKR_HD bool pack_fits_game(int ticks, int live, int winner) {
+  return ((unsigned)ticks < 65536u) & ((unsigned)live < 2u) & ((unsigned)winner < 4u);
+}
+
+// ---- admission to the steady loop for the rest of a launch.  A state that
+// fits the packed form now keeps fitting it for `left` more ticks under
+// split_tick_carry's integer rules if the configuration passes admit_cfg and
+// the post-tick state admit_player / admit_game:
+//   positions  change only to one that passed fits_board against a room of at
+//              most 255, to the player's (a fired projectile), or to a restart
+//              position (the host's restart_fits);
+//   qcd        is <= 0 (fires: becomes cdmax, or cdmax - 1 in a live game) or
+//              counts down by one per live tick: within [-128, 127] at entry,
+//              it stays within [min(entry, -1), max(entry, cdmax)];
+//   qage       grows by one per live tick while qcd counts down and restarts
+//              from 0 at a fire, so qage + max(qcd, 0) never grows except to
+//              max(cdmax, 1) at a fire: at most 255 at entry, at most 255 later;
+//   ticks      grows by at most one per tick, or restarts from 0;
+//   qvalid, live, winner only take the values the tick writes (0 / 1, 0 / 1,
+//              0 .. 2).
+// tests/steady_admit_check.cpp runs the recurrence over every entry.
+// (admit_cfg: for a configuration that passed cfg_ok, whose differences cannot wrap)
+SKR_HD bool admit_cfg(int W, int H, int psize, int qsize, int cdmax) {
+  return (cdmax >= 0) & (cdmax <= 127) & (W - psize <= 255) & (H - psize <= 255) & (W - qsize <= 255) &
+         (H - qsize <= 255);
+}
+SKR_HD bool admit_player(int px, int py, int qx, int qy, int cd, int age, int qv) {
+  // (unsigned sums: no wrap to undefined behaviour for a state that does not fit, which the first term rejects)
+  return (int)pack_fits_player(px, py, qx, qy, cd, age, qv) & (int)((unsigned)age + (unsigned)(cd > 0 ? cd : 0) <= 255u);
+}
+// left: the ticks of the launch after this one
+SKR_HD bool admit_game(int ticks, int live, int winner, int left) {
+  return (int)pack_fits_game(ticks, live, winner) & (int)((unsigned)left <= 65535u) &
+         (int)((unsigned)ticks + ((unsigned)left & 0xffffu) <= 65535u);
+}
+
 }  // namespace skrange
