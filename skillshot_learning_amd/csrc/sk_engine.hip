@@ -159,8 +159,15 @@ static constexpr int64_t kSplitPackMaxEnvs = 98304;
 // fp64 carry runs under the loads for nothing
 // (profiles/r09_split_fast_sweep.jsonl)
 static constexpr int kFastSplitMinTicks = 100;
-// the steady loop's rest between a tick's stores and the next tick's loads, in units of 64 cycles (k_step_split_multi)
-static constexpr int kSteadyRest = 7;
+// the steady loop's rest between a tick's stores and the next tick's loads, in units of 64 cycles
+// (k_step_split_multi).  7 while the collision test stood in front of the stores; with the test
+// behind them the tail is longer by itself and the best rest drops to 3 (DESIGN 4.1, round 16;
+// profiles/r16_rest_sweep.jsonl)
+static constexpr int kSteadyRest = 3;
+// the steady tick's chain, from the state wait to the last state store, at issue priority 1: the
+// partner wave's work under its own loads no longer takes the chain's slots
+// (profiles/r16_bench_ab.jsonl)
+static constexpr bool kSteadyPrio = true;
 // SK_CTR_STRIDE slots per wave of the widest step grid (k_step_split: two
 // lanes per game), at least SK_COUNTER_SLOTS
 static inline int64_t counter_slots(int64_t n) {
@@ -1223,6 +1230,17 @@ __device__ __forceinline__ void split_store_pack(const MultiArgs& a, __amdgpu_bu
     __builtin_amdgcn_raw_buffer_store_b64((skb2i){pos, cah}, rp, o + 2u * plane, 0, 16);
   }
 }
+// ... the {pack_pos, pack_cah} word alone (the steady tick's corrected flags)
+template <int POL>
+__device__ __forceinline__ void split_store_pack_word(const MultiArgs& a, __amdgpu_buffer_rsrc_t rp,
+                                                      const SplitLane& L, int pos, int cah) {
+  if constexpr (POL == 0) {
+    reinterpret_cast<skb2i*>(a.pack)[4 * a.n + L.h] = (skb2i){pos, cah};
+  } else {
+    const uint32_t o = (uint32_t)L.h * 8u, plane = (uint32_t)a.n * 16u;
+    __builtin_amdgcn_raw_buffer_store_b64((skb2i){pos, cah}, rp, o + 2u * plane, 0, 16);
+  }
+}
 // OBS (the full contract, sk_env_step_multi_obs): the tick also evaluates
 // the exact sincos of the post-look rotation (the obs epilogue's projectile
 // sincos when it fires, and the next tick's carried move sincos: no
@@ -1260,6 +1278,18 @@ __device__ __forceinline__ void split_store_pack(const MultiArgs& a, __amdgpu_bu
 // move's and the projectile's bounds, the collision's intervals) take one
 // unsigned compare each (sk_range.hpp; the host admits a launch to the steady
 // loop only for a configuration where that form is exact, skrange::cfg_ok).
+// The steady tick stores its state ahead of the collision test, as if nobody
+// were hit: once the move, the fire, the projectile step and the clock are
+// settled it exchanges the partner's `qvalid` and stores the three planes with
+// `live` and `winner` as loaded; the exchanges of qx / qy, box_hit, the bit's
+// exchange and pair_hit follow in the tail, where the wave rests anyway
+// (kSteadyRest).  A hit makes the game `done`: inside the `any_done` block a
+// game hit in this tick that does not restart stores its {pos, cah} word
+// again (a restarting one all three planes, as before), after the first store
+// in program order, from the same lane to the same address.  From the state
+// wait to the last state store the full-wave tick has 113 instructions on its
+// common path for 146 (profiles/r16_listing.txt), and that stretch runs at
+// issue priority 1 (kSteadyPrio).
 //
 // FULL (STEADY only): every lane of the wave is in range, `L.in` is true at
 // compile time: no lane mask around the key check, the stores
@@ -1522,7 +1552,28 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
     opx = pair_swap(px);
     opy = pair_swap(py);
   }
-  const int oqx = pair_swap(qx), oqy = pair_swap(qy), oqv = pair_swap(qvalid);
+  int oqx, oqy, oqv;
+  if constexpr (STEADY) {
+    // The steady tick stores its state here, ahead of the collision test, with
+    // `live` and `winner` as loaded: on a tick without a hit (all but about
+    // one wave-tick in forty) that is the tick's result, and the test, its
+    // three exchanges and the selects run behind the stores, in the stretch
+    // the wave rests anyway.  A game hit in this tick is `done`: the cold
+    // block below stores its {pos, cah} word again (the restart all three
+    // planes), from the same lane to the same address in program order.
+    oqv = pair_swap(qvalid);
+    const bool qch = __double_as_longlong(qrot) != __double_as_longlong(q_old);
+    const unsigned hi = p ? pack_flags(oqv, qvalid, live, winner) : (unsigned)ticks;
+    if (in) split_store_pack<POL>(a, rp, L, rot, qrot, qch, pack_pos(px, py, qx, qy), pack_cah(qcd, qage, hi));
+    if constexpr (kSteadyPrio) __builtin_amdgcn_s_setprio(0);  // (raised behind the state wait: steady_tick)
+    __builtin_amdgcn_sched_barrier(0);  // (the test stays behind the stores)
+    oqx = pair_swap(qx);
+    oqy = pair_swap(qy);
+  } else {
+    oqx = pair_swap(qx);
+    oqy = pair_swap(qy);
+    oqv = pair_swap(qvalid);
+  }
   if constexpr (PACK) {
     // the packed forms: one test per lane, "my player is hit by the partner's
     // projectile", and the pair exchanges the bit (skrange::pair_hit); the
@@ -1556,7 +1607,9 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
                                (int)skrange::admit_game(ticks, live, winner, left));
     *admit = to_pack && __ballot(!adm) == 0;
   }
-  if (PACK && to_pack) {  // the packed halves out before done / restart
+  if constexpr (STEADY) {
+    // (stored above, ahead of the collision test)
+  } else if (PACK && to_pack) {  // the packed halves out before done / restart
     const bool qch = (!STEADY && !packed) || __double_as_longlong(qrot) != __double_as_longlong(q_old);
     const unsigned hi = p ? pack_flags(oqv, qvalid, live, winner) : (unsigned)ticks;
     if (in) split_store_pack<POL>(a, rp, L, rot, qrot, qch, pack_pos(px, py, qx, qy), pack_cah(qcd, qage, hi));
@@ -1623,6 +1676,14 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
     if (PACK && to_pack) {
       const unsigned hi = p ? pack_flags(ov, qvalid, live, winner) : (unsigned)ticks;
       if (rs) split_store_pack<POL>(a, rp, L, rot, qrot, true, pack_pos(px, py, qx, qy), pack_cah(qcd, qage, hi));
+      if constexpr (STEADY) {
+        // a game hit in this tick that does not restart: its flags (player 2's
+        // lane) went out above as loaded, the word again with the hit in it
+        // (`ov` is its `oqv`: nothing of it was reset).  Done by the tick
+        // limit alone, or dead before the tick: nothing to correct.
+        if (d && !rs && lv && !live && p)
+          split_store_pack_word<POL>(a, rp, L, pack_pos(px, py, qx, qy), pack_cah(qcd, qage, hi));
+      }
     } else if (rs) {
       const unsigned fl = (unsigned)(qvalid & 0xff) | ((unsigned)(ov & 0xff) << 8) | ((unsigned)(live & 0xff) << 16) |
                           ((unsigned)(winner & 0xff) << 24);
@@ -1768,6 +1829,15 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
         split_pre_pin(pre);
       }
       __builtin_amdgcn_sched_barrier(0);
+      if constexpr (kSteadyPrio) {
+        // The chain from here to the last state store at issue priority 1
+        // (split_tick_carry lowers it behind the stores).  The empty asm
+        // takes the loaded state: the state wait stands in front of it, so
+        // the wave does not wait at the raised priority.
+        asm volatile("" : "+v"(w.rot.x), "+v"(w.rot.y), "+v"(w.qrot.x), "+v"(w.qrot.y), "+v"(w.pp.x), "+v"(w.pp.y));
+        __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_sched_barrier(0);
+      }
       split_tick_carry<POL, false, true, FAST, true, decltype(full)::value>(a, c, r, L, wc, 0, step0 + (uint64_t)t, w,
                                                                             cur, tc, false, rp, packed, &S, &pre);
       // The wave rests kSteadyRest x 64 cycles between its stores and the
@@ -1780,7 +1850,10 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
       // (0: 1.89, 3: 1.77, 4: 1.72, 5: 1.68, 6: 1.66-1.67, 7: 1.65-1.66,
       // 10: 1.71 us; profiles/r11_steady_rest_sweep.txt; with SplitPre under
       // the loads 0: 1.81, 3: 1.69, 4: 1.64, 5: 1.60, 6: 1.57, 7: 1.56-1.57,
-      // 8: 1.57-1.58, 10: 1.58-1.59; profiles/r12_rest_sweep.jsonl).  The fp64-carry
+      // 8: 1.57-1.58, 10: 1.58-1.59; profiles/r12_rest_sweep.jsonl; with the
+      // collision test behind the stores and the chain at priority 1 the tail
+      // rests for the wave: 2: 1.36, 3: 1.36-1.37, 4: 1.37-1.39, 5: 1.39,
+      // 6: 1.40-1.41, 7: 1.39-1.40, 8: 1.43; profiles/r16_rest_sweep.jsonl).  The fp64-carry
       // form (the launches under kFastSplitMinTicks ticks) does not rest: its
       // 20-tick launch reads the parent's figure without, and 3.7 % more with
       // (profiles/r11_bench_ab_norest.jsonl, r11_bench_ab_rest_both.jsonl).
