@@ -583,7 +583,7 @@ __device__ __forceinline__ void tick_env_fast(const Cfg& c, Env& e, float a0_mov
 // holds one wave: with two or three co-resident waves whatever a wave issues
 // adds to the tick, which is why the step-only split tick carries the fp32
 // sincos_fast and integer steps instead, split_tick_carry's FAST form in
-// sk_engine.hip).  Each value is KEYED by the
+// sk_multi.hpp).  Each value is KEYED by the
 // rotation it is the sincos of and used only where the key equals the
 // rotation just loaded (bitwise); any lane that misses (tick 0 of a launch)
 // sends its wave through the full evaluation.  The state still makes its

@@ -1,5 +1,5 @@
 // sk_range.hpp — the integer range tests of the packed split kernel's steady
-// tick (k_step_split_multi, sk_engine.hip), host- and device-compilable so
+// tick (k_step_split_multi, sk_multi.hpp), host- and device-compilable so
 // tests/pair_collision_check.cpp checks these very functions on the CPU.
 //
 // A closed-interval test lo <= v <= hi costs two signed compares and an AND.
@@ -64,7 +64,7 @@ SKR_HD PairHit pair_hit(bool lv, bool hit_p1, bool hit_p2) {
   return r;
 }
 
-// ---- the packed form's ranges (pack_pos / pack_cah, sk_engine.hip): a byte
+// ---- the packed form's ranges (pack_pos / pack_cah, sk_multi.hpp): a byte
 // per coordinate, a signed byte of cooldown, a byte of age, 16 bits of ticks
 SKR_HD bool pack_fits_player(int px, int py, int qx, int qy, int cd, int age, int qv) {
   return ((unsigned)px < 256u) & ((unsigned)py < 256u) & ((unsigned)qx < 256u) & ((unsigned)qy < 256u) &

@@ -1,5 +1,5 @@
 // sk_step.hpp — device pieces of the fused env step shared by the step
-// kernels (sk_engine.hip) and the self-play tick that runs the actor forward
+// kernels (sk_engine.hip, sk_multi.hpp) and the self-play tick that runs the actor forward
 // in the same launch (sk_learn32.hip, k_act_step32): launch geometry, the
 // episode counters, the device step counter, the step's argument block, the
 // replay ring insert's arrival, and k_step_split's per-lane body.

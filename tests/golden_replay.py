@@ -14,12 +14,13 @@ GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 def fixture_names():
     """Trajectory fixtures (boards.npz and probes.npz hold single states, see
-    test_board_cpu / test_closed_forms_cpu)."""
+    test_board_cpu / test_closed_forms_cpu; multi_plan.npz holds no game at
+    all but the multi-tick step's launch decisions, see test_multi_plan_cpu)."""
     return sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, "*.npz"))
-                  if os.path.basename(p) not in SINGLE_STATE)
+                  if os.path.basename(p) not in NO_TRAJECTORY)
 
 
-SINGLE_STATE = ("boards.npz", "probes.npz")
+NO_TRAJECTORY = ("boards.npz", "probes.npz", "multi_plan.npz")
 
 
 def probe_state(d):

@@ -1,7 +1,7 @@
 // Host check of the packed split kernel's launch-long admission to its steady
 // loop (csrc/sk_range.hpp: admit_cfg, admit_player, admit_game, and the
 // pack_fits_* tests they imply), compiled for the CPU.  The tick's integer
-// rules are modelled here as split_tick_carry states them (sk_engine.hip):
+// rules are modelled here as split_tick_carry states them (sk_multi.hpp):
 //
 //   f = qcd <= 0;  if (f) { qcd = cdmax; qage = 0; qvalid = 1; }
 //   ticks += lv;  qcd -= lv;  qage += lv;          lv: the game is live

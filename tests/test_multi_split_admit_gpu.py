@@ -4,8 +4,9 @@ enters the loop only if no state of it can stop fitting the packed form in
 the ticks that remain, and the steady tick then carries no fit test and no
 exchange-format stores.  One step_multi launch of 12 ticks must equal 12
 single steps bit for bit: state planes, every tick's done / winner row, the
-RNG step counter and the episode counters (the pattern, helpers and fixtures
-of tests/test_multi_split_collide_gpu.py: SK_MULTI_SPLIT=1, SK_MULTI_PACK=1,
+RNG step counter and the episode counters (the pattern and helpers of
+tests/test_multi_split_collide_gpu.py, the fixtures and the forcing of
+tests/multi_split_cases.py: SK_MULTI_SPLIT=1, SK_MULTI_PACK=1,
 both trig forms, both state ports, both workgroup sizes; 1, 31, 32, 33 and 65
 games).  Tick 0 and tick 11 run the generic tick, ticks 1..10 the steady loop
 where the wave is admitted.
@@ -36,7 +37,8 @@ import torch
 
 import oracle.pyoracle as pyoracle
 from oracle.pyoracle import PyOracle
-from test_multi_split_collide_gpu import P1, P2, T, _check, _env, block, fast, pol, ssa  # noqa: F401
+from multi_split_cases import _env, block, fast, pol  # noqa: F401
+from test_multi_split_collide_gpu import P1, P2, T, _check, ssa  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 

@@ -37,6 +37,7 @@ import torch
 
 from oracle.pyoracle import PyOracle
 from test_multi_fast_trig_gpu import PSPEED, move_safe
+from multi_split_cases import _env, block, fast, pol  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -60,29 +61,6 @@ def ssa():
     assert (cfg.board_w, cfg.board_h, cfg.player_size, cfg.projectile_size) == (250, 250, 5, 3)
     assert (cfg.player_speed, cfg.projectile_speed, cfg.cooldown_max) == (PSPEED, 5, 15)
     return m
-
-
-@pytest.fixture(params=["64", "512"], ids=["block64", "block512"])
-def block(request):
-    return request.param
-
-
-@pytest.fixture(params=[0, 1], ids=["plain", "write_through"])
-def pol(request):
-    return request.param
-
-
-@pytest.fixture(params=["0", "1"], ids=["fp64carry", "fast"])
-def fast(request):
-    return request.param
-
-
-def _env(monkeypatch, pol, block, fast):
-    monkeypatch.setenv("SK_MULTI_SPLIT", "1")
-    monkeypatch.setenv("SK_MULTI_PACK", "1")
-    monkeypatch.setenv("SK_MULTI_FAST", fast)
-    monkeypatch.setenv("SK_MULTI_POLICY", str(pol))
-    monkeypatch.setenv("SK_MULTI_BLOCK", block)
 
 
 def _layout(n, n_ticks=T, last_steady_only=False):

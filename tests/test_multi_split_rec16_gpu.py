@@ -24,6 +24,7 @@ import torch
 from oracle.pyoracle import Game, PyOracle
 from test_multi_fast_trig_gpu import (FAST_RANGE, LOOK, PSPEED, QSPEED, _tie_rotations, clampf, fired_safe,
                                       move_safe, sincos_fast)
+from multi_split_cases import _env, block, fast, pol  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -37,29 +38,6 @@ def ssa():
     cfg = m._capi.default_config()
     assert (cfg.player_speed, cfg.projectile_speed, cfg.look_speed) == (PSPEED, QSPEED, LOOK)
     return m
-
-
-@pytest.fixture(params=["64", "512"], ids=["block64", "block512"])
-def block(request):
-    return request.param
-
-
-@pytest.fixture(params=[0, 1], ids=["plain", "write_through"])
-def pol(request):
-    return request.param
-
-
-@pytest.fixture(params=["0", "1"], ids=["fp64carry", "fast"])
-def fast(request):
-    return request.param
-
-
-def _env(monkeypatch, pol, block, fast):
-    monkeypatch.setenv("SK_MULTI_SPLIT", "1")
-    monkeypatch.setenv("SK_MULTI_PACK", "1")
-    monkeypatch.setenv("SK_MULTI_FAST", fast)
-    monkeypatch.setenv("SK_MULTI_POLICY", str(pol))
-    monkeypatch.setenv("SK_MULTI_BLOCK", block)
 
 
 def _pair(ssa, n, seed, tick_limit, edit=None):

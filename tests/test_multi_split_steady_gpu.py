@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+from multi_split_cases import _env, block, fast, pol  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 
@@ -21,29 +23,6 @@ def ssa():
     import skillshot_learning_amd as m
     m.load_library()
     return m
-
-
-@pytest.fixture(params=["64", "512"], ids=["block64", "block512"])
-def block(request):
-    return request.param
-
-
-@pytest.fixture(params=[0, 1], ids=["plain", "write_through"])
-def pol(request):
-    return request.param
-
-
-@pytest.fixture(params=["0", "1"], ids=["fp64carry", "fast"])
-def fast(request):
-    return request.param
-
-
-def _env(monkeypatch, pol, block, fast):
-    monkeypatch.setenv("SK_MULTI_SPLIT", "1")
-    monkeypatch.setenv("SK_MULTI_PACK", "1")
-    monkeypatch.setenv("SK_MULTI_FAST", fast)
-    monkeypatch.setenv("SK_MULTI_POLICY", str(pol))
-    monkeypatch.setenv("SK_MULTI_BLOCK", block)
 
 
 def _pair(ssa, n, seed, tick_limit, random_positions=True):
