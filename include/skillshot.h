@@ -60,7 +60,17 @@ enum {
 };
 
 /* Game constants; sk_config_default() fills the reference values
- * (SkillshotGame.py:11, Player.py:9-15, Projectile.py:5-10). */
+ * (SkillshotGame.py:11, Player.py:9-15, Projectile.py:5-10).
+ * Limits (sk_env_create / sk_env_attach return SK_EINVAL otherwise): board
+ * sides in [1, 2^20]; box sizes >= 1 and no larger than either side; speeds,
+ * fixed starts and the random range within +-2^20; cooldown_max in [1, 2^20];
+ * rand_hi > rand_lo; look_speed finite, within +-2^20.  The obs distances are
+ * normalised by (2 * board_w^2)^0.5, the board's width alone, also where
+ * board_w != board_h (SkillshotLearner.py:43 is a literal of the 250 x 250
+ * board).  Every admitted configuration computes the reference's results;
+ * the fp32-trig kernels serve |look_speed| <= pi/4 and the packed multi-tick
+ * form boards with side - box <= 255, cooldown_max <= 127 and start
+ * positions below 256 (other configurations run the fp64 / unpacked forms). */
 typedef struct sk_config {
   int32_t board_w, board_h;          /* 250, 250 */
   int32_t player_size;               /* 5 (5x5 box) */

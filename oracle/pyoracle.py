@@ -27,10 +27,26 @@ import math
 
 import numpy as np
 
+# the reference's constants: what a Config holds where it is given nothing else (read when it is made)
 BOARD = 250
 PLAYER_SIDE, PROJ_SIDE = 5, 3
 MOVE, LOOK, PROJ_SPEED, COOLDOWN = 3, 0.25, 5, 15
-MAX_DIST = (2 * BOARD ** 2) ** 0.5  # SkillshotLearner.py:43
+
+
+class Config:
+    """The game constants a Game plays under: sk_config's fields (include/skillshot.h) by name, the
+    reference's values by default.  `config` may be None, a dict of field names or an object with them."""
+
+    def __init__(self, config=None):
+        default = dict(board_w=BOARD, board_h=BOARD, player_size=PLAYER_SIDE, projectile_size=PROJ_SIDE,
+                       player_speed=MOVE, projectile_speed=PROJ_SPEED, cooldown_max=COOLDOWN, look_speed=LOOK,
+                       fixed_p1_x=50, fixed_p1_y=50, fixed_p2_x=200, fixed_p2_y=200, rand_lo=25, rand_hi=225)
+        for k, v in default.items():
+            got = v if config is None else config.get(k, v) if isinstance(config, dict) else getattr(config, k)
+            setattr(self, k, float(got) if k == "look_speed" else int(got))
+        # SkillshotLearner.py:43 is the literal of the reference's own board; the rule on any other
+        # board (the engine's and the C oracle's too): the board's WIDTH alone, also where W != H
+        self.max_dist = (2 * self.board_w ** 2) ** 0.5
 
 
 def _clamp_unit(v):
@@ -42,8 +58,8 @@ def _clamp_unit(v):
     return v
 
 
-def _fits(x, y, side):
-    return 0 <= x and x + side <= BOARD and 0 <= y and y + side <= BOARD
+def _fits(c, x, y, side):
+    return 0 <= x and x + side <= c.board_w and 0 <= y and y + side <= c.board_h
 
 
 def _gradient(r):
@@ -65,10 +81,11 @@ def _quirk_angle(r):
 
 class Game:
     """One game's state as plain Python values (players indexed 0 / 1)."""
-    __slots__ = ("x", "y", "rot", "qx", "qy", "qrot", "qcd", "qage", "qvalid", "ticks", "live", "winner")
+    __slots__ = ("c", "x", "y", "rot", "qx", "qy", "qrot", "qcd", "qage", "qvalid", "ticks", "live", "winner")
 
-    def __init__(self):
-        self.x, self.y, self.rot = [50, 200], [50, 200], [0.0, 0.0]
+    def __init__(self, config=None):
+        c = self.c = config if isinstance(config, Config) else Config(config)
+        self.x, self.y, self.rot = [c.fixed_p1_x, c.fixed_p2_x], [c.fixed_p1_y, c.fixed_p2_y], [0.0, 0.0]
         self.qx, self.qy, self.qrot = [0, 0], [0, 0], [0.0, 0.0]
         self.qcd, self.qage, self.qvalid = [0, 0], [0, 0], [False, False]
         self.ticks, self.live, self.winner = 0, True, 0
@@ -77,24 +94,24 @@ class Game:
     def move_direction(self, p, speed):
         s = _clamp_unit(speed)
         sn, cs = math.sin(self.rot[p]), math.cos(self.rot[p])
-        nx = int(round(self.x[p] - sn * MOVE * s))
-        ny = int(round(self.y[p] - cs * MOVE * s))
-        if _fits(nx, ny, PLAYER_SIDE):
+        nx = int(round(self.x[p] - sn * self.c.player_speed * s))
+        ny = int(round(self.y[p] - cs * self.c.player_speed * s))
+        if _fits(self.c, nx, ny, self.c.player_size):
             self.x[p], self.y[p] = nx, ny
 
     def move_look(self, p, angle):
-        self.rot[p] += _clamp_unit(angle) * LOOK
+        self.rot[p] += _clamp_unit(angle) * self.c.look_speed
 
     def shoot(self, p):
         if self.qcd[p] <= 0:
             self.qx[p], self.qy[p], self.qrot[p] = self.x[p], self.y[p], self.rot[p]
-            self.qvalid[p], self.qcd[p], self.qage[p] = True, COOLDOWN, 0
+            self.qvalid[p], self.qcd[p], self.qage[p] = True, self.c.cooldown_max, 0
 
     # -- game
     def _projectile_tick(self, p):
-        nx = int(round(self.qx[p] - math.sin(self.qrot[p]) * PROJ_SPEED))
-        ny = int(round(self.qy[p] - math.cos(self.qrot[p]) * PROJ_SPEED))
-        if self.qvalid[p] and _fits(nx, ny, PROJ_SIDE):
+        nx = int(round(self.qx[p] - math.sin(self.qrot[p]) * self.c.projectile_speed))
+        ny = int(round(self.qy[p] - math.cos(self.qrot[p]) * self.c.projectile_speed))
+        if self.qvalid[p] and _fits(self.c, nx, ny, self.c.projectile_size):
             self.qx[p], self.qy[p] = nx, ny
         else:
             self.qvalid[p] = False
@@ -105,6 +122,7 @@ class Game:
         """player p touched by the opponent's projectile: some corner of the
         projectile box (x in {qx+3, qx}, y in {qy, qy-3}) inside p's box"""
         q = 1 - p
+        PROJ_SIDE, PLAYER_SIDE = self.c.projectile_size, self.c.player_size
         if not self.qvalid[q]:
             return False
         xs = (self.qx[q] + PROJ_SIDE, self.qx[q])
@@ -129,6 +147,7 @@ class Game:
     # -- observation
     def _future(self, p):
         o = 1 - p
+        PROJ_SIDE, PLAYER_SIDE = self.c.projectile_size, self.c.player_size
         if not self.qvalid[p]:
             return False
         g = _gradient(self.qrot[p])
@@ -158,21 +177,24 @@ class Game:
 
     def observe(self, p, reward_kind=0):
         f = self.features(p)
-        obs = [f[2] / MAX_DIST, f[3] / MAX_DIST, f[4] / BOARD, f[5] / BOARD, _quirk_angle(f[6]),
-               f[7] / COOLDOWN, f[16] / MAX_DIST, f[11] / BOARD, f[12] / BOARD, _quirk_angle(f[13]),
+        c = self.c
+        MAX_DIST, W, H = c.max_dist, c.board_w, c.board_h
+        obs = [f[2] / MAX_DIST, f[3] / MAX_DIST, f[4] / W, f[5] / H, _quirk_angle(f[6]),
+               f[7] / c.cooldown_max, f[16] / MAX_DIST, f[11] / W, f[12] / H, _quirk_angle(f[13]),
                f[10] / MAX_DIST, int(f[17])]
         if reward_kind == 1:  # simple: own projectile distance minus the opponent's
             reward = f[16] - self.features(1 - p)[16]
         else:  # looking: -(own line distance) / board size
-            reward = -f[2] / BOARD
+            reward = -f[2] / W
         return obs, reward
 
 
 class PyOracle:
     """N games with the engine-protocol methods of tests/golden_replay.replay."""
 
-    def __init__(self, n):
-        self.games = [Game() for _ in range(n)]
+    def __init__(self, n, config=None):
+        self.config = Config(config)
+        self.games = [Game(self.config) for _ in range(n)]
 
     def load(self, a):
         pos, rot, qpos, qrot = (np.asarray(a[k]) for k in ("pos", "rot", "qpos", "qrot"))

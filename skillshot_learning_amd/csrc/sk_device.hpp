@@ -28,9 +28,16 @@ struct Cfg {  // device copy of sk_config (kernel argument)
   int W, H, psize, qsize, pspeed, qspeed, cdmax;
   double look;
   int f1x, f1y, f2x, f2y, rlo, rhi;
-  double max_dist;  // (2*250**2)**0.5, SkillshotLearner.py:43
+  double max_dist;  // (2*W**2)**0.5: SkillshotLearner.py:43's literal at W = 250; the board's width alone
   double inv_max_dist, inv_W, inv_H, inv_cdmax;  // obs scalings as products (rounded to f32 anyway)
+  // |rotation| below which a fired projectile's step may be decided from
+  // sktrig::sincos_add: sincos_fast's range (kFastRotMax), or -1 (never) for a
+  // configuration whose look step can leave sincos_add's range, |look| > pi/4
+  double fast_rot_max;
 };
+
+constexpr double kFastRotMax = 1647099.3291652855;  // sktrig::sincos_fast's range, 2^20 * pi/2
+using sktrig::look_fits_add;  // (sk_trig.hpp) the host's gate: to_dcfg, the launch plan's knobs, the one-tick variant
 
 struct View {  // device pointers, layout of include/skillshot.h
   int4* pos;
@@ -517,7 +524,7 @@ __device__ __forceinline__ void tick_env_fast(const Cfg& c, Env& e, sktrig::SinC
   const float ex0 = t0.s * qs, ey0 = t0.c * qs;
   const float ex1 = t1.s * qs, ey1 = t1.c * qs;
   const bool v0 = (e.qvalid[0] != 0) || f0, v1 = (e.qvalid[1] != 0) || f1;  // valid after shoot
-  const int safe = (int)okm & ((int)f0 | (int)okq0) & ((int)f1 | (int)okq1) & (int)round_safe(dx0, em) &
+  const int safe = (int)okm & (int)(c.fast_rot_max > 0.0) & ((int)f0 | (int)okq0) & ((int)f1 | (int)okq1) & (int)round_safe(dx0, em) &
                    (int)round_safe(dy0, em) & (int)round_safe(dx1, em) & (int)round_safe(dy1, em) &
                    ((int)!v0 | ((int)round_safe(ex0, eq) & (int)round_safe(ey0, eq))) &
                    ((int)!v1 | ((int)round_safe(ex1, eq) & (int)round_safe(ey1, eq)));
@@ -668,9 +675,9 @@ __device__ __forceinline__ void tick_env_carry(const Cfg& c, Env& e, TrigCarry& 
   const sktrig::SinCosF u0 = sktrig::sincos_add(sktrig::SinCosF{(float)t.m[0].s, (float)t.m[0].c}, l0 * lk);
   const sktrig::SinCosF u1 = sktrig::sincos_add(sktrig::SinCosF{(float)t.m[1].s, (float)t.m[1].c}, l1 * lk);
   const float ex0 = u0.s * qs, ey0 = u0.c * qs, ex1 = u1.s * qs, ey1 = u1.c * qs;
-  const bool un0 = f0 && !((int)(fabs(e.rot[0]) < 1647099.3291652855) & (int)round_safe(ex0, eq) &
+  const bool un0 = f0 && !((int)(fabs(e.rot[0]) < c.fast_rot_max) & (int)round_safe(ex0, eq) &
                                  (int)round_safe(ey0, eq));
-  const bool un1 = f1 && !((int)(fabs(e.rot[1]) < 1647099.3291652855) & (int)round_safe(ex1, eq) &
+  const bool un1 = f1 && !((int)(fabs(e.rot[1]) < c.fast_rot_max) & (int)round_safe(ex1, eq) &
                                  (int)round_safe(ey1, eq));
   sktrig::SinCos t0 = t.tq[0], t1 = t.tq[1];  // in flight: the carried exact values
   bool fast0 = f0, fast1 = f1;
@@ -751,10 +758,12 @@ __device__ __forceinline__ double dist_line_point(double g, int lx, int ly, int 
 }
 
 // SkillshotGame.get_dist_point_point (SkillshotGame.py:132-134): exact integer
-// sum of squares, then sqrt (correctly rounded)
+// sum of squares, then sqrt (correctly rounded).  The squares and their sum
+// in fp64, exact for differences below 2^26: an int sum wraps once a
+// difference passes 46,340, on a board sk_config admits (up to 2^20)
 __device__ __forceinline__ double dist_point_point(int ax, int ay, int bx, int by) {
-  int dx = ax - bx, dy = ay - by;
-  return sqrt((double)(dx * dx + dy * dy));
+  const double dx = (double)(ax - bx), dy = (double)(ay - by);
+  return sqrt(dx * dx + dy * dy);
 }
 
 // SkillshotGame.check_future_collision (SkillshotGame.py:96-113) for a
@@ -952,8 +961,10 @@ __device__ __forceinline__ unsigned obs_env(const Cfg& c, const Env& e, float o0
 //   ~5e-7 of obs[0] (/ max_dist) and of the looking reward (/ W), far inside
 //   the 1e-5 obs bar.  For the projectile, r = qrot and `qt` is the fp64
 //   sincos the tick moved it with (its rotation after shoot, Player.py:80-84).
-// * get_dist_point_point (:132-134): sqrtf of the exact integer sum of
-//   squares (< 2^24), relative error 6e-8.
+// * get_dist_point_point (:132-134): sqrtf of the sum of squares, taken in
+//   fp32 (an int sum wraps on a board past 46,340): exact below 2^24, as on
+//   the reference's board, three roundings of 2^-24 above; relative error
+//   below 2e-7.
 // * check_future_collision (:96-113) needs g itself within a few ulp of
 //   math.tan(-qrot + pi/2): the argument y = fl(kPi2 - qrot) is pi/2 - (qrot +
 //   eta) with eta = (pi/2 - kPi2) + the sum's rounding error (TwoSum, exact),
@@ -976,15 +987,16 @@ __device__ __forceinline__ void obs12_sc(const Cfg& c, int px, int py, double ro
                                          int qy, double qrot, sktrig::SinCos qt, int qcd, int qvalid, int ox, int oy,
                                          float out[12], float* path_dist, bool* amb, double* gq = nullptr) {
   const int dx = ox - px, dy = oy - py, ex = ox - qx, ey = oy - qy;
-  const float pd = fabsf(fmaf(pr.c, (float)dx, -(pr.s * (float)dy)));
+  const float fdx = (float)dx, fdy = (float)dy, fex = (float)ex, fey = (float)ey;
+  const float pd = fabsf(fmaf(pr.c, fdx, -(pr.s * fdy)));
   *path_dist = pd;
   out[0] = (float)((double)pd * c.inv_max_dist);
-  out[1] = (float)((double)sqrtf((float)(dx * dx + dy * dy)) * c.inv_max_dist);
+  out[1] = (float)((double)sqrtf(fdx * fdx + fdy * fdy) * c.inv_max_dist);
   out[2] = (float)((double)px * c.inv_W);
   out[3] = (float)((double)py * c.inv_H);
   out[4] = (float)(((py_mod2_fast(rot) * kPi) / 2.0) * kPi);  // `% 2 * np.pi) / 2 * np.pi`
   out[5] = (float)((double)qcd * c.inv_cdmax);
-  out[6] = (float)((double)sqrtf((float)(ex * ex + ey * ey)) * c.inv_max_dist);
+  out[6] = (float)((double)sqrtf(fex * fex + fey * fey) * c.inv_max_dist);
   out[7] = (float)((double)qx * c.inv_W);
   out[8] = (float)((double)qy * c.inv_H);
   out[9] = (float)(((py_mod2_fast(qrot) * kPi) / 2.0) * kPi);

@@ -578,6 +578,7 @@ static Cfg to_dcfg(const sk_config& s) {
   c.inv_W = 1.0 / (double)s.board_w;
   c.inv_H = 1.0 / (double)s.board_h;
   c.inv_cdmax = 1.0 / (double)s.cooldown_max;
+  c.fast_rot_max = look_fits_add(s.look_speed) ? kFastRotMax : -1.0;
   return c;
 }
 
@@ -593,10 +594,25 @@ static int check_device(int32_t device) {
   return SK_OK;
 }
 
+// The limits of sk_config (include/skillshot.h): what the
+// kernels' int arithmetic holds without wrapping (skrange::kCfgMax = 2^20:
+// sums of a few coordinates, sizes and steps stay far inside int; squared
+// distances are taken in floating point), for both backends.
 static int validate_cfg(const sk_config& c) {
+  const int M = skrange::kCfgMax;
+  const auto mag_ok = [](int v) { return v >= -M && v <= M; };
   if (c.board_w <= 0 || c.board_h <= 0 || c.player_size <= 0 || c.projectile_size <= 0 ||
       c.cooldown_max <= 0 || c.rand_hi <= c.rand_lo)
     return fail(SK_EINVAL, "invalid sk_config");
+  if (c.board_w > M || c.board_h > M || c.cooldown_max > M || !mag_ok(c.player_speed) ||
+      !mag_ok(c.projectile_speed) || !mag_ok(c.fixed_p1_x) || !mag_ok(c.fixed_p1_y) || !mag_ok(c.fixed_p2_x) ||
+      !mag_ok(c.fixed_p2_y) || !mag_ok(c.rand_lo) || !mag_ok(c.rand_hi))
+    return fail(SK_EINVAL, "sk_config: a board side, speed, cooldown or start position beyond 2^20");
+  if (c.player_size > c.board_w || c.player_size > c.board_h || c.projectile_size > c.board_w ||
+      c.projectile_size > c.board_h)
+    return fail(SK_EINVAL, "sk_config: a box larger than the board");
+  if (!(std::fabs(c.look_speed) <= 1048576.0))  // (also refuses NaN)
+    return fail(SK_EINVAL, "sk_config: look_speed not finite or beyond 2^20");
   return SK_OK;
 }
 
@@ -1027,11 +1043,15 @@ static int step_launch(sk_env* e, const float* actions, float* obs, float* rewar
   // k_step_split when observations are written (65,536 games with obs: 9.8
   // vs 10.5 us; profiles/r01g_step_variants.jsonl, r01v_step_block_ab.jsonl).
   // The ring insert is k_step_split's.
-  const int variant = ring ? 1
-                      : e->step_variant >= 0 ? e->step_variant
-                      : (e->n >= kFastStepMinEnvs && e->n < kFastStepMaxEnvs) ? 2
-                      : e->n >= kFastStepMaxEnvs ? 0
-                      : (obs || reward || obs_reset || e->n <= kSplitStepMaxEnvs) ? 1 : 0;
+  // A look step past sincos_add's range (look_fits_add): k_step_fast would
+  // send every firing lane through its fp64 redo, so such a configuration
+  // runs k_step where it would have run k_step_fast, forced or not.
+  const int chosen = ring ? 1
+                     : e->step_variant >= 0 ? e->step_variant
+                     : (e->n >= kFastStepMinEnvs && e->n < kFastStepMaxEnvs) ? 2
+                     : e->n >= kFastStepMaxEnvs ? 0
+                     : (obs || reward || obs_reset || e->n <= kSplitStepMaxEnvs) ? 1 : 0;
+  const int variant = chosen == 2 && !look_fits_add(e->cfg.look_speed) ? 0 : chosen;
   if (variant == 1)
     k_step_split<<<step_grid(2 * (int64_t)e->n), kStepBlock, 0, (hipStream_t)stream>>>(a, e->dcfg);
   else if (variant == 2)
@@ -1364,6 +1384,11 @@ static int step_multi(sk_env* e, const float* actions, int64_t ring_slabs, int64
                  skrange::cfg_ok(dc.W, dc.H, dc.psize, dc.qsize, dc.pspeed, dc.qspeed) &&
                  skrange::admit_cfg(dc.W, dc.H, dc.psize, dc.qsize, dc.cdmax);
   pi.knobs = e->knobs;
+  // the fp32-trig instantiations take a fired projectile's step from
+  // sincos_add: not for a look step past its range (look_fits_add), forced
+  // (SK_MULTI_FAST=1) or not; the fp64-carry ones then evaluate it exactly
+  // (Cfg::fast_rot_max)
+  if (!look_fits_add(dc.look)) pi.knobs.fast = 0;
 
   // ---- the plan, and the pack buffer if it packs
   skplan::MultiPlan plan = skplan::plan_multi(pi);

@@ -229,8 +229,9 @@ inline double dist_line_point(double g, int lx, int ly, int cx, int cy) {  // Sk
 }
 
 inline double dist_point_point(int ax, int ay, int bx, int by) {  // SkillshotGame.py:132-134
-  const int dx = ax - bx, dy = ay - by;
-  return std::sqrt((double)(dx * dx + dy * dy));
+  // (fp64 squares, exact below 2^26: an int sum wraps once a difference passes 46,340)
+  const double dx = (double)(ax - bx), dy = (double)(ay - by);
+  return std::sqrt(dx * dx + dy * dy);
 }
 
 // SkillshotGame.check_future_collision (SkillshotGame.py:96-113), x_dir gate
@@ -256,7 +257,8 @@ inline double py_mod2(double r) {  // Python float % 2 (floored)
 // prepare_states (SkillshotLearner.py:512-543) of player p; path_dist for the reward
 void obs12(const sk_config& c, const Env& e, int p, float out[12], double* path_dist) {
   const int o = 1 - p;
-  const double md = std::sqrt(2.0 * (double)c.board_w * (double)c.board_w);  // :43 (square board)
+  // :43 is the literal of the reference's 250 x 250 board; the rule here: the board's width alone
+  const double md = std::sqrt(2.0 * (double)c.board_w * (double)c.board_w);
   const double gp = grad(e.rot[p]), gq = grad(e.qrot[p]);
   const double pd = dist_line_point(gp, e.px[p], e.py[p], e.px[o], e.py[o]);
   *path_dist = pd;

@@ -1009,7 +1009,7 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
     unq = f && !sktrig::fast_step_delta(u, tc.mok, qsf).safe;  // its deltas are ex, ey
     un = !dm.safe || unq || (qvalid && !f && tc.qex);
   } else {
-    un = f && !((int)(fabs(rot) < 1647099.3291652855) & (int)round_safe(ex, eq) & (int)round_safe(ey, eq));
+    un = f && !((int)(fabs(rot) < c.fast_rot_max) & (int)round_safe(ex, eq) & (int)round_safe(ey, eq));
     tt = tc.tq;  // in flight: the carried exact value
     tm = tc.m;
   }

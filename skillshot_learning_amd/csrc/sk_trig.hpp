@@ -150,7 +150,7 @@ SKT_HD SinCosF sincos_fast(double x, bool* ok) {
 }
 
 // sin/cos of r + d from fp32 sin/cos of r (|error| <= SKT_FAST_ERR) and a
-// small exact fp32 d (|d| <= pi/4): the angle-addition formulas.  The fast
+// small exact fp32 d (|d| <= pi/4, look_fits_add below): the angle-addition formulas.  The fast
 // tick uses it for a projectile fired this tick, whose rotation is the
 // player's rotation plus the look action times 0.25 (Player.py:33-39; the
 // fp64 sum's own rounding, <= 3e-14 at |r| <= 500, is far below the bound).
@@ -164,6 +164,18 @@ SKT_HD SinCosF sincos_add(SinCosF r, float d) {
   o.s = fmaf(r.s, k.c, r.c * k.s);
   o.c = fmaf(r.c, k.c, -(r.s * k.s));
   return o;
+}
+
+// The configurations whose fired projectiles sincos_add may decide: its
+// argument is l * look_speed with the look action |l| <= 1, and its bound
+// holds on [-pi/4, pi/4] only (at look_speed 1.0 the error is already 6.3e-7,
+// at 3.0 it is 4.5e-2 and one firing tick in 80 steps to the wrong cell with
+// round_safe satisfied; tests/fast_step_check.cpp sweeps it).  Launch-uniform,
+// so the host decides: for any other look_speed (NaN included) no kernel takes
+// a fired projectile's step from sincos_add (sk_engine.hip: to_dcfg's
+// Cfg::fast_rot_max, the multi-tick plan's knobs, the one-tick variant).
+SKT_HD bool look_fits_add(double look_speed) {
+  return (int)(look_speed >= -0.78539816339744831) & (int)(look_speed <= 0.78539816339744831);
 }
 
 // true iff d is provably not within `eps` of a half-integer, so that

@@ -104,7 +104,50 @@ static void both_speeds(double rot, float am, float al, int p, int q) {
   check(rot, am, al, p, q, 5, 3);
 }
 
+// The look-step sweep ("look" as the first argument): for each look_speed,
+// `count` random (rotation, look action) pairs at projectile speed 5: the
+// fired projectile's fp32 decision q - rintf(d) against nearbyint(q - sin(r +
+// l * look) * 5) in fp64.  `wrong`: decisions the engine takes from the fp32
+// path (look_fits_add(look_speed), the host's gate, and fast_step_delta's
+// safe) that differ from the fp64 one: must be 0.  `raw_wrong`: the same
+// without the gate, i.e. what sincos_add alone would decide; `max_err`:
+// sincos_add's largest error against sinl / cosl.  One line per look_speed.
+static int look_sweep(long count) {
+  const double looks[] = {0.25, 0.4, 0.78, 0.8, 1.0, 1.5, 3.0};
+  long total_wrong = 0;
+  for (double look : looks) {
+    const bool gate = sktrig::look_fits_add(look);
+    long wrong = 0, raw_wrong = 0, safe_n = 0;
+    double max_err = 0.0;
+    for (long i = 0; i < count; ++i) {
+      const double rot = uni(-600.0, 600.0);
+      const float l = clampf((float)uni(-1.25, 1.25));
+      const int q = (int)(next() % 251);
+      bool ok;
+      const sktrig::SinCosF m = sktrig::sincos_fast(rot, &ok);
+      const double rn = rot + (double)l * look;
+      const sktrig::SinCosF u = sktrig::sincos_add(m, l * (float)look);
+      const double es = fabs((double)((long double)u.s - sinl((long double)rn)));
+      const double ec = fabs((double)((long double)u.c - cosl((long double)rn)));
+      max_err = fmax(max_err, fmax(es, ec));
+      const sktrig::FastDelta d = sktrig::fast_step_delta(u, ok, 5.0f);
+      if (!d.safe) continue;
+      ++safe_n;
+      const sktrig::SinCos X = exact(rn);
+      const bool differs = nearbyint((double)q - X.s * 5.0) != (double)(q - (int)rintf(d.x)) ||
+                           nearbyint((double)q - X.c * 5.0) != (double)(q - (int)rintf(d.y));
+      raw_wrong += differs;
+      wrong += gate && differs;
+    }
+    printf("look=%g gate=%d n=%ld safe=%ld max_err=%.3e wrong=%ld raw_wrong=%ld\n", look, (int)gate, count, safe_n,
+           max_err, wrong, raw_wrong);
+    total_wrong += wrong;
+  }
+  return total_wrong ? 1 : 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && argv[1][0] == 'l') return look_sweep(argc > 2 ? atol(argv[2]) : 4000000);
   const long count = argc > 1 ? atol(argv[1]) : 10000000;
   // random play: game rotations, actions past the clamp, board positions
   for (long i = 0; i < count; ++i) {

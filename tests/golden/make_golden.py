@@ -4,6 +4,7 @@ Test infrastructure only.  Run in the build container (where the read-only
 reference checkout lives at /root/reference):
 
     python3 -B tests/golden/make_golden.py
+    python3 -B tests/golden/make_golden.py --only config    # the cfg_*.npz fixtures (scenario_config)
 
 It imports the reference's game core (SkillshotGame.py / Player.py /
 Projectile.py) and, because SkillshotLearner.py imports TensorFlow at module
@@ -68,7 +69,9 @@ class LearnerStub:
     def __init__(self, game):
         self.game_environment = game
         self.player_ids = (1, 2)
-        self.max_dist_normaliser = (2 * (250 ** 2)) ** 0.5
+        # SkillshotLearner.py:43 is this literal at 250, the reference's own board; on another
+        # board the engine's stated rule: the same expression of the board's width
+        self.max_dist_normaliser = (2 * (game.board_size[0] ** 2)) ** 0.5
 
     def prepare_states(self, states, pid):
         return _M["prepare_states"](self, states, pid)
@@ -181,7 +184,7 @@ def run_env(game, actions, tick_limit, protocol="learner", shoot=None, run_after
     return snaps, obs, rew, rsim, t, full
 
 
-def pack(name, inits, acts, results, tick_limit, protocol, shoot=None, note=""):
+def pack(name, inits, acts, results, tick_limit, protocol, shoot=None, note="", extra=None):
     E = len(results)
     Tm = max(r[4] for r in results)
     if protocol == "learner":
@@ -241,6 +244,7 @@ def pack(name, inits, acts, results, tick_limit, protocol, shoot=None, note=""):
     out["obs"] = series(1)
     out["reward"] = series(2)
     out["reward_simple"] = series(3)
+    out.update(extra or {})
     path = os.path.join(OUT, name + ".npz")
     np.savez_compressed(path, **out)
     print(f"{name}: E={E} max_ticks={Tm} -> {os.path.getsize(path)} bytes")
@@ -491,6 +495,109 @@ def scenario_raw(seed=19):
         results.append(run_env(g, a, 2 ** 31 - 1, protocol="raw", shoot=s, run_after_done=40))
     pack("raw", inits, acts, results, 2 ** 31 - 1, "raw", shoot=shoots,
          note="per-method calls, sparse shooting, stepping continues 40 ticks after game end")
+
+
+# ---- the reference at other constants than its own (cfg_*.npz).  The
+# reference keeps them as class attributes (Player.py:9-15, Projectile.py:5-10)
+# and as the board size of a game and its four objects, so a configuration is
+# applied by assignment from here, restored after each scenario; no reference
+# text is edited or copied.  Fields in sk_config's order (include/skillshot.h).
+CFG_INT_FIELDS = ("board_w", "board_h", "player_size", "projectile_size", "player_speed", "projectile_speed",
+                  "cooldown_max", "fixed_p1_x", "fixed_p1_y", "fixed_p2_x", "fixed_p2_y", "rand_lo", "rand_hi")
+CFG_DEFAULT = dict(board_w=250, board_h=250, player_size=5, projectile_size=3, player_speed=3, projectile_speed=5,
+                   cooldown_max=15, look_speed=0.25, fixed_p1_x=50, fixed_p1_y=50, fixed_p2_x=200, fixed_p2_y=200,
+                   rand_lo=25, rand_hi=225)
+# (the same table as tests/config_cases.py, which says what each one is for)
+CONFIGS = dict(
+    cfg_wide=dict(board_w=320, board_h=180, fixed_p2_x=260, fixed_p2_y=140, rand_hi=175),
+    cfg_packed=dict(board_w=140, board_h=230, player_size=7, projectile_size=4, player_speed=4, projectile_speed=6,
+                    cooldown_max=9, look_speed=0.4, fixed_p1_x=20, fixed_p1_y=30, fixed_p2_x=110, fixed_p2_y=190,
+                    rand_lo=10, rand_hi=130),
+    cfg_look08=dict(look_speed=0.8),
+    cfg_look3=dict(look_speed=3.0),
+    cfg_fast=dict(player_size=12, projectile_size=1, player_speed=11, projectile_speed=23, cooldown_max=127),
+    cfg_cd128=dict(cooldown_max=128),
+    cfg_huge=dict(board_w=60000, board_h=50000, player_speed=3000, projectile_speed=9000, fixed_p1_x=5000,
+                  fixed_p1_y=4000, fixed_p2_x=55000, fixed_p2_y=45000, rand_lo=1000, rand_hi=49000),
+)
+
+
+@contextlib.contextmanager
+def reference_constants(cfg):
+    Player, Projectile = sys.modules["Player"].Player, sys.modules["Projectile"].Projectile
+    saved = [(Player, k, getattr(Player, k)) for k in ("speed_move", "speed_look", "shape_image")] + \
+            [(Projectile, k, getattr(Projectile, k)) for k in ("cooldown_max", "speed_move", "shape_image")]
+    Player.speed_move, Player.speed_look = cfg["player_speed"], cfg["look_speed"]
+    Player.shape_image = [[1] * cfg["player_size"] for _ in range(cfg["player_size"])]  # only its side is read
+    Projectile.cooldown_max, Projectile.speed_move = cfg["cooldown_max"], cfg["projectile_speed"]
+    Projectile.shape_image = [[1] * cfg["projectile_size"] for _ in range(cfg["projectile_size"])]
+    try:
+        yield
+    finally:
+        for obj, k, v in saved:
+            setattr(obj, k, v)
+
+
+def config_game(cfg, init):
+    g = SkillshotGame()  # built under reference_constants: the shape sizes are read at construction
+    dim = (cfg["board_w"], cfg["board_h"])
+    g.board_size = dim
+    for pl in (g.player1, g.player2):
+        pl.board_dim = dim
+        pl.projectile.board_dim = dim
+    set_state(g, init)
+    return g
+
+
+def scenario_config(name=None, cfg=None, seed=41, T=200):
+    """6-8 games of at most 200 ticks under the learner protocol at one
+    non-default configuration: random play from random integer starts, two
+    games pushed into the walls and two with the players aimed at each other
+    (hits).  Starts are explicit (set_state): the reference hard-codes its own."""
+    if name is None:  # --only config: all of them
+        for i, (nm, over) in enumerate(CONFIGS.items()):
+            scenario_config(nm, dict(CFG_DEFAULT, **over), seed=41 + i)
+        return
+    rng = random.Random(seed)
+    W, H, ps = cfg["board_w"], cfg["board_h"], cfg["player_size"]
+    inits, acts, results = [], [], []
+
+    def start(p1, p2, rot):
+        init = fixed_init()
+        init["pos"], init["rot"] = [list(p1), list(p2)], list(rot)
+        return init
+
+    games = []
+    for e in range(4):  # random play; (cfg_huge: the starts lie tens of thousands apart)
+        p1 = [rng.randrange(0, W // 4), rng.randrange(0, H - ps + 1)]
+        p2 = [rng.randrange(3 * W // 4, W - ps + 1), rng.randrange(0, H - ps + 1)]
+        if e % 2:
+            p1, p2 = p2, p1
+        games.append((start(p1, p2, [rng.uniform(-4, 4), rng.uniform(-4, 4)]), f32_uniform(rng, (T, 2, 2))))
+    for e, c in enumerate([[0, 0], [W - ps, H - ps]]):  # pushed into the walls from two corners
+        a = f32_uniform(rng, (T, 2, 2))
+        a[:, 0, 0] = np.where(a[:, 0, 0] > -0.5, 1.0, a[:, 0, 0])
+        a[:, 0, 1] = a[:, 0, 1] * 0.1
+        games.append((start(c, [W // 2, H // 2], [rng.uniform(-4, 4), rng.uniform(-4, 4)]), a))
+    for e in range(2):  # aimed at each other, a few projectile steps apart, standing almost still
+        d = cfg["projectile_speed"] * rng.randrange(3, 7)
+        ang = rng.uniform(-math.pi, math.pi)
+        x1, y1 = W // 2, H // 2
+        dx, dy = int(round(-math.sin(ang) * d)), int(round(-math.cos(ang) * d))
+        a = f32_uniform(rng, (T, 2, 2), -0.02, 0.02)
+        a[:, :, 1] *= min(1.0, 0.25 / cfg["look_speed"])
+        games.append((start([x1, y1], [x1 + dx, y1 + dy], [ang, ang + math.pi]), a))
+    with reference_constants(cfg):
+        for init, a in games:
+            g = config_game(cfg, init)
+            inits.append(snapshot(g))
+            acts.append(a)
+            results.append(run_env(g, a, T))
+    pack(name, inits, acts, results, T, "learner", note=f"non-default sk_config, seed {seed}",
+         extra=dict(config_i=np.array([cfg[k] for k in CFG_INT_FIELDS], np.int32),
+                    config_look=np.float64(cfg["look_speed"])))
+    wins = [r[0][-1]["winner"] for r in results]
+    print(f"  {name}: winners {wins} steps {[r[4] for r in results]}")
 
 
 if __name__ == "__main__" and "--only" in sys.argv:  # one scenario: --only NAME (e.g. bigrot)

@@ -23,6 +23,41 @@ def fixture_names():
 NO_TRAJECTORY = ("boards.npz", "probes.npz", "multi_plan.npz")
 
 
+# sk_config's fields (include/skillshot.h) as the cfg_* fixtures store them: `config_i`, the
+# thirteen integers in the struct's order, and `config_look`, look_speed
+CFG_INT_FIELDS = ("board_w", "board_h", "player_size", "projectile_size", "player_speed", "projectile_speed",
+                  "cooldown_max", "fixed_p1_x", "fixed_p1_y", "fixed_p2_x", "fixed_p2_y", "rand_lo", "rand_hi")
+CFG_DEFAULT = dict(board_w=250, board_h=250, player_size=5, projectile_size=3, player_speed=3, projectile_speed=5,
+                   cooldown_max=15, look_speed=0.25, fixed_p1_x=50, fixed_p1_y=50, fixed_p2_x=200, fixed_p2_y=200,
+                   rand_lo=25, rand_hi=225)
+
+
+def config_of(d):
+    """The configuration fixture `d` was generated at, as a dict of sk_config field names (the
+    reference's own constants where the fixture names none).  Both oracles take the dict;
+    sk_config() makes the engine's struct of it."""
+    if "config_i" not in d:
+        return dict(CFG_DEFAULT)
+    c = {k: int(v) for k, v in zip(CFG_INT_FIELDS, d["config_i"])}
+    c["look_speed"] = float(d["config_look"])
+    return c
+
+
+def sk_config(cfg):
+    """dict of sk_config field names (missing ones default) -> the engine's SkConfig"""
+    from skillshot_learning_amd import _capi
+    c = _capi.default_config()
+    for k, v in cfg.items():
+        assert hasattr(c, k), k
+        setattr(c, k, v)
+    return c
+
+
+def max_dist_of(cfg):
+    """the obs distances' normaliser: (2 * board_w ** 2) ** 0.5, the board's width alone"""
+    return (2 * cfg["board_w"] ** 2) ** 0.5
+
+
 def probe_state(d):
     """Engine-layout arrays of the probe boards (probes.npz): live game, tick 0, no winner."""
     n = d["pos"].shape[0]

@@ -80,7 +80,7 @@ def step_variant(request, monkeypatch):
 @pytest.mark.parametrize("name", gr.fixture_names())
 def test_golden_fixture(ssa, name, step_variant):
     d = gr.load(name)
-    n = gr.replay(GpuEngine(ssa, d["pos"].shape[0]), d, obs_tol=OBS_TOL)
+    n = gr.replay(GpuEngine(ssa, d["pos"].shape[0], config=gr.sk_config(gr.config_of(d))), d, obs_tol=OBS_TOL)
     assert n == int(d["n_steps"].sum())
 
 
@@ -304,7 +304,8 @@ def test_full_reward_on_engine_features(ssa, name):
     from skillshot_learning_amd.learner import calculate_rewards_full
     d = gr.load(name)
     E, T = d["pos"].shape[0], int(d["n_steps"].max())
-    g = ssa.VecSkillshotGame(E, tick_limit=int(d["tick_limit"]))
+    cfg = gr.config_of(d)
+    g = ssa.VecSkillshotGame(E, tick_limit=int(d["tick_limit"]), config=gr.sk_config(cfg))
     g.load_state_dict(gr.state_at(d, 0))
     feats, wins = [], []
     for t in range(T):
@@ -314,7 +315,8 @@ def test_full_reward_on_engine_features(ssa, name):
         wins.append(out["winner"].long())
     f = torch.stack(feats)
     lengths = torch.as_tensor(d["n_steps"].astype(np.int64)).cuda()
-    r, raised = calculate_rewards_full(f[..., 16], f[..., 17] != 0, f[..., 14].long(), torch.stack(wins), lengths)
+    r, raised = calculate_rewards_full(f[..., 16], f[..., 17] != 0, f[..., 14].long(), torch.stack(wins), lengths,
+                                       max_dist=gr.max_dist_of(cfg))
     want = d["reward_full"]
     want_raised = np.isnan(want[:, 0, 0])
     assert np.array_equal(raised.cpu().numpy(), want_raised)
@@ -454,7 +456,7 @@ def test_golden_fixture_multi_obs(ssa, monkeypatch, name, pol):
     E = d["pos"].shape[0]
     n_steps = d["n_steps"]
     T = int(n_steps.max())
-    g = ssa.VecSkillshotGame(E, tick_limit=int(d["tick_limit"]))
+    g = ssa.VecSkillshotGame(E, tick_limit=int(d["tick_limit"]), config=gr.sk_config(gr.config_of(d)))
     g.load_state_dict(gr.state_at(d, 0))
     acts = np.ascontiguousarray(np.transpose(d["actions"][:, :T], (1, 2, 0, 3)))  # [T, 2, E, 2]
     out = g.step_multi_obs(torch.as_tensor(acts, dtype=torch.float32).cuda(), auto_reset=False)

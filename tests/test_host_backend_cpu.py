@@ -26,8 +26,8 @@ def ssa():
 class CpuEngine:
     """golden_replay's engine protocol over VecSkillshotGame(device="cpu")"""
 
-    def __init__(self, ssa, n):
-        self.g = ssa.VecSkillshotGame(n, device="cpu")
+    def __init__(self, ssa, n, config=None):
+        self.g = ssa.VecSkillshotGame(n, device="cpu", config=config)
 
     def load(self, arrays):
         self.g.load_state_dict(arrays)
@@ -65,7 +65,7 @@ class CpuEngine:
 @pytest.mark.parametrize("name", gr.fixture_names())
 def test_cpu_backend_golden_fixture(ssa, name):
     d = gr.load(name)
-    n = gr.replay(CpuEngine(ssa, d["pos"].shape[0]), d, obs_tol=OBS_TOL)
+    n = gr.replay(CpuEngine(ssa, d["pos"].shape[0], gr.sk_config(gr.config_of(d))), d, obs_tol=OBS_TOL)
     assert n == int(d["n_steps"].sum())
 
 

@@ -32,8 +32,13 @@ def kit():
     return dict(ssa=ssa, learner=learner, nets=nets, kernels=kernels, PLANES=PLANES)
 
 
-def fresh_env(kit, n):
-    g = kit["ssa"].VecSkillshotGame(n, device="cuda", seed=ENV_SEED, tick_limit=LIMIT)
+def fresh_env(kit, n, config=None):
+    """config: a name of tests/config_cases.py's table (None: the reference's constants)"""
+    cfg = None
+    if config is not None:
+        import config_cases
+        cfg = config_cases.sk_config(config)
+    g = kit["ssa"].VecSkillshotGame(n, device="cuda", seed=ENV_SEED, tick_limit=LIMIT, config=cfg)
     g.step_counter = 0
     g.reset(random_positions=True)
     return g
@@ -42,16 +47,16 @@ def fresh_env(kit, n):
 _LOOPS = {}
 
 
-def loop_reference(kit, n, reward, swapped):
+def loop_reference(kit, n, reward, swapped, config=None):
     """the per-tick loop, once per case (shared, never modified): lengths, the
     loop's fp32 acc += r over live games, every plane and the obs of each
     game at the moment it ended (the loop keeps moving ended games' players;
     the snapshots stop with the game), and the loop's iterations"""
-    key = (n, reward, swapped)
+    key = (n, reward, swapped, config)
     if key in _LOOPS:
         return _LOOPS[key]
     k1, k2 = kit["kernels"][::-1] if swapped else kit["kernels"]
-    g = fresh_env(kit, n)
+    g = fresh_env(kit, n, config)
     start = g.state_dict()
     obs, _ = g.observe()
     obs0 = obs.clone()
@@ -122,6 +127,26 @@ def test_act_match_equals_per_tick_loop(kit, monkeypatch, n, reward, swapped):
         other = loop_reference(kit, n, reward, not swapped)  # the seats swapped: another match
         assert not torch.equal(m["lengths"], other["lengths"])
         assert not torch.equal(bits(m["returns"]), bits(other["returns"]))
+
+
+def test_act_match_equals_per_tick_loop_at_cfg_packed(kit, monkeypatch):
+    """the match kernel instantiates the step on its own: one case (37 games) at a configuration in which
+    every constant differs from the reference's (tests/config_cases.py: cfg_packed)"""
+    monkeypatch.setenv("SK_FWD16", "0")
+    n, reward = 37, "looking"
+    ref = loop_reference(kit, n, reward, False, config="cfg_packed")
+    k1, k2 = kit["kernels"]
+    g = fresh_env(kit, n, "cfg_packed")
+    g.load_state_dict(ref["start"])
+    c0 = g.step_counter
+    m = g.act_match(k1, k2, ref["obs0"], n_ticks=LIMIT + 20, reward=reward)
+    torch.cuda.synchronize()
+    assert_same_match(kit, g, m, ref)
+    T = int(m["lengths"].max())
+    assert T == ref["iters"] and g.step_counter == c0 + T == ref["step_counter"]
+    # (and it is another match than the reference configuration's)
+    assert not torch.equal(m["lengths"], loop_reference(kit, n, reward, False)["lengths"]) or \
+        not torch.equal(bits(m["returns"]), bits(loop_reference(kit, n, reward, False)["returns"]))
 
 
 def test_act_match_in_chunks(kit, monkeypatch):

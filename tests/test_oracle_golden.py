@@ -7,8 +7,8 @@ import golden_replay as gr
 
 
 class OracleEngine:
-    def __init__(self, oracle, n):
-        self.s = oracle.OracleState(n)
+    def __init__(self, oracle, n, config=None):
+        self.s = oracle.OracleState(n, config=config)
 
     def load(self, arrays):
         self.s.load(arrays)
@@ -43,7 +43,7 @@ def test_oracle_matches_reference(oracle_mod, name):
     d = gr.load(name)
     # the oracle uses libm pow like CPython: it must agree far tighter than the
     # engine's 1e-5 obs tolerance
-    n = gr.replay(OracleEngine(oracle_mod, d["pos"].shape[0]), d, obs_tol=1e-12)
+    n = gr.replay(OracleEngine(oracle_mod, d["pos"].shape[0], gr.config_of(d)), d, obs_tol=1e-12)
     assert n == int(d["n_steps"].sum())
 
 

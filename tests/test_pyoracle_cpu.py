@@ -19,7 +19,7 @@ TOL = 1e-12
 @pytest.mark.parametrize("name", gr.fixture_names())
 def test_pyoracle_matches_reference(name):
     d = gr.load(name)
-    n = gr.replay(PyOracle(d["pos"].shape[0]), d, obs_tol=TOL)
+    n = gr.replay(PyOracle(d["pos"].shape[0], gr.config_of(d)), d, obs_tol=TOL)
     assert n == int(d["n_steps"].sum())
 
 

@@ -233,6 +233,19 @@ def test_act_step_equals_actor_then_step_insert(learner, monkeypatch, n, noise, 
     partial last 16-game tile; 302: N % 4 != 0, the two-launch fallback).
     tile 16: k_act_step16 (8 games per workgroup, SK_ACT16=1) against the
     16-row forward (SK_FWD16=1)"""
+    _act_step_equals_actor_then_step_insert(learner, monkeypatch, n, noise, tile)
+
+
+def test_act_step_equals_actor_then_step_insert_at_cfg_packed(learner, monkeypatch):
+    """sk_env_act_step instantiates the step on its own: one case (300 games, no noise) at a configuration
+    in which every constant differs from the reference's (tests/config_cases.py: cfg_packed)"""
+    import config_cases
+    _act_step_equals_actor_then_step_insert(learner, monkeypatch, 300, "none", "32",
+                                            config=config_cases.sk_config("cfg_packed"))
+
+
+def _act_step_equals_actor_then_step_insert(learner, monkeypatch, n, noise, tile, config=None):
+    """the body of test_act_step_equals_actor_then_step_insert; config: an sk_config (None: the reference's)"""
     from skillshot_learning_amd.actor_kernel import ActorKernel32
     from skillshot_learning_amd.vec_env import VecSkillshotGame
     monkeypatch.setenv("SK_FWD16", "1" if tile == "16" else "0")
@@ -241,7 +254,7 @@ def test_act_step_equals_actor_then_step_insert(learner, monkeypatch, n, noise, 
     actor = learner.Actor().cuda()
     sd, asd = {"none": (0.0, 0.0), "param": (0.5, 0.0), "action": (0.0, 0.15)}[noise]
     ks = [ActorKernel32(actor, seed=9) for _ in range(2)]
-    envs = [VecSkillshotGame(n, device="cuda", seed=11, tick_limit=30) for _ in range(2)]
+    envs = [VecSkillshotGame(n, device="cuda", seed=11, tick_limit=30, config=config) for _ in range(2)]
     rings = [learner.ReplayRing(1 << 13, "cuda", seed=3) for _ in range(2)]
     obs = [e.observe()[0].clone() for e in envs]
     for t in range(45):

@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from golden_replay import fixture_names, load, state_at
+from golden_replay import config_of, fixture_names, load, max_dist_of, state_at
 from skillshot_learning_amd.learner import calculate_rewards_full
 
 FULL = [n for n in fixture_names() if "reward_full" in np.load(f"tests/golden/{n}.npz").files]
@@ -27,7 +27,7 @@ def _inputs(oracle_mod, d):
     T = int(d["n_steps"].max())
     feats = []
     for t in range(1, T + 1):
-        st = oracle_mod.OracleState(E)
+        st = oracle_mod.OracleState(E, config=config_of(d))
         st.load(state_at(d, t))
         feats.append(st.features())
     f = torch.from_numpy(np.stack(feats))                       # [T, E, 2, 18]
@@ -48,7 +48,7 @@ def test_full_reward_fixtures_present():
 def test_calculate_rewards_full_matches_reference(oracle_mod, name):
     d = load(name)
     dist, fc, age, winner, lengths = _inputs(oracle_mod, d)
-    r, raised = calculate_rewards_full(dist, fc, age, winner, lengths)
+    r, raised = calculate_rewards_full(dist, fc, age, winner, lengths, max_dist=max_dist_of(config_of(d)))
     want = d["reward_full"]                                     # [E, T, 2]
     want_raised = np.isnan(want[:, 0, 0])
     assert np.array_equal(raised.numpy(), want_raised)
