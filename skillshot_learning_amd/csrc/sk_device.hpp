@@ -895,10 +895,18 @@ __device__ __forceinline__ double py_mod2(double r) {  // Python float % 2 (floo
   return m;
 }
 
-// Python's float r % 2 (floored, +0.0 for exact multiples): r - 2*floor(r/2)
-// is exact for every finite r (the product by 0.5 and by 2 are exact, and the
-// subtraction is exact or rounds the same single result fmod(r,2) + 2 does).
-__device__ __forceinline__ double py_mod2_fast(double r) { return r - 2.0 * floor(r * 0.5); }
+// Python's float r % 2 (floored, +0.0 for exact multiples): r - 2*floor(r/2).
+// The product by 2 is exact, and the product by 0.5 is for every finite r but
+// the odd multiples of the least subnormal, which round to even; then the
+// subtraction is exact or rounds the same single result fmod(r,2) + 2 does.
+// Of those, only r = -5e-324 halves to a value with another floor: -0.0, so
+// the difference is r itself where Python gives 2.0.  No other finite r
+// leaves a negative difference; the select puts that one into [0, 2] too
+// (tests/test_device_numerics_gpu.py: every edge, bit for bit).
+__device__ __forceinline__ double py_mod2_fast(double r) {
+  const double m = r - 2.0 * floor(r * 0.5);
+  return (m < 0.0) ? m + 2.0 : m;
+}
 
 __device__ __attribute__((noinline)) double tan_lib(double y) { return tan(y); }
 

@@ -1,6 +1,7 @@
 """csrc/sk_tan_cr.hpp compiled for the host (same -ffp-contract=off as the
-kernels; the device evaluates the same IEEE operations, fma = v_fma_f64)
-against a 70-digit Decimal tan: every result correctly rounded.  The
+kernels; tests/test_device_numerics_gpu.py holds the device build to the same
+bits and to the same Decimal tan) against a 70-digit Decimal tan: every
+result correctly rounded.  The
 arguments are the game's tan inputs -rot + pi/2 over the rotation ranges
 play reaches, multiples of pi/4 (gradients 0, +-1, ~1.6e16) and near them."""
 import math

@@ -1,7 +1,9 @@
 """Host check of the step kernels' trig (csrc/sk_trig.hpp), compiled for the
 CPU with the kernels' flags: sincos_bf within 1 ulp of glibc (the reference's
 math.sin/cos), sincos_fast within SKT_FAST_ERR/2 of long-double sinl/cosl —
-the bound the fp32 fast tick's exact-fallback threshold is derived from."""
+the bound the fp32 fast tick's exact-fallback threshold is derived from.
+These bounds reach the device through tests/test_device_numerics_gpu.py: the
+device build of the same functions equals the host build bit for bit."""
 import os
 import subprocess
 

@@ -1,6 +1,7 @@
 // CPU check of the step kernels' trig (skillshot_learning_amd/csrc/sk_trig.hpp,
-// compiled here for the host with the same -ffp-contract=off; the device
-// code evaluates the same IEEE operations, fmaf = v_fma_f32, rint = v_rndne).
+// compiled here for the host with the same -ffp-contract=off; that the device
+// build gives the same bits, values and flags, is what
+// tests/test_device_numerics_gpu.py checks element by element).
 //   sincos_bf   : |error| <= 1 ulp against glibc sin/cos (the reference's
 //                 math.sin / math.cos), exact at +-0
 //   sincos_fast : |error| <= SKT_FAST_ERR / 2 against long-double sinl/cosl
