@@ -1,5 +1,5 @@
 """numpy restatement of the fp32 actor's noisy forward: the exploration noise
-of k_actor_fwd32 / k_actor_fwd16 (csrc/sk_learn32.hip, actor_tile32 /
+of k_actor_fwd32 / k_actor_fwd16 (csrc/sk_act32.hpp, actor_tile32 /
 actor_tile16) as a pure function of (seed, call, global row, unit).
 
 TEST INFRASTRUCTURE ONLY (see oracle/keras_ref.py): no torch, no GPU, nothing
@@ -18,7 +18,7 @@ What the kernels draw, restated:
         u2 = (w >> 8) 2^-24           revolutions (exact)
         z  = [r0 cos0, r0 sin0, r1 cos1, r1 sin1],  r = sqrt(-2 ln u1)
     everything after u1 / u2 in the evaluation dtype.
-  * Layers 1 and 2: ROUNDS_PARAM = 7 rounds (SK_F32_NOISE_ROUNDS), row key
+  * Layers 1 and 2: ROUNDS_PARAM = 7 rounds (kF32NoiseRounds), row key
     4 (row // 4), row r takes z[r % 4]; unit u for layer 1, 256 + u for
     layer 2.  Layer 3: 10 rounds, row key = the row, unit 384, outputs 0 / 1
     take z[0] / z[1].  Action noise: 10 rounds, row key = the row, unit 385,

@@ -74,7 +74,7 @@ class ActorKernel:
 
 
 class ActorKernel32:
-    """The actor forward at the reference's precision (csrc/sk_learn32.hip
+    """The actor forward at the reference's precision (csrc/sk_act32.hpp
     k_actor_fwd32 / k_actor_fwd16), reading biases and W3 from the actor's
     flat fp32 parameter vector and W1 / W2 from its split pack (`pack`,
     sk_split.hpp: three bf16 pieces per weight, so the 32-row tile computes

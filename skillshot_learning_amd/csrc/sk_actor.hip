@@ -35,11 +35,9 @@ using namespace skmlp;
 // both accumulators fit the 512-register budget without spilling (332 VGPRs;
 // 8 waves force 256 and 77 spilled: 61 -> 72 us at 131,072 rows,
 // profiles/r02_actor_threads_ab.jsonl)
-#ifndef SK_NOISE_THREADS  // A/B builds only
-#define SK_NOISE_THREADS 256
-#endif
+constexpr int kNoiseThreads = 256;
 template <bool NOISE>
-constexpr int threads_for() { return NOISE ? SK_NOISE_THREADS : 512; }
+constexpr int threads_for() { return NOISE ? kNoiseThreads : 512; }
 
 
 // ---------------------------------------------------------------- packing

@@ -59,24 +59,22 @@ __host__ __device__ __forceinline__ int w2_k(int kk, int h, int j) {
 
 // ---------------------------------------------------------------- noise
 // Philox rounds of the bf16 actor's parameter-noise draws (normals16 /
-// pairs8; A/B builds override).  Philox4x32-7 is the fewest rounds of the
+// pairs8).  Philox4x32-7 is the fewest rounds of the
 // family that pass TestU01 BigCrush (Salmon et al., SC'11; 10 is the library
 // default, kept as a safety margin everywhere else: the fp32 path's layer 3,
 // the Dropout masks, the replay sampling, action noise; the fp32 path's
-// layers 1 / 2 also draw with 7, SK_F32_NOISE_ROUNDS).  The noisy bf16
+// layers 1 / 2 also draw with 7, kF32NoiseRounds).  The noisy bf16
 // forward is VALU-issue-bound (~29 % of its cycles were Philox's 64-bit
 // multiplies): 7 rounds take the 131,072-row launch 60.4 -> 55.8 us
 // (profiles/r03y3_bf16_noise_pair_philox_ab.jsonl).  What pins the noise:
-// the fp32 path's (sk_learn32.hip normals4 / noisy4: 24-bit uniforms, 7
+// the fp32 path's (sk_act32.hpp normals4 / noisy4: 24-bit uniforms, 7
 // rounds in layers 1 / 2, 10 in layer 3 and the action noise) is keyed --
 // every row and output against the fp64 restatement of (seed, call, row,
 // unit), oracle/noise_ref.py, tests/test_actor_noise_keyed_gpu.py; this
 // bf16 set's normals16 / pairs8 (16-bit uniforms, keys through the fragment
 // layout) stay pinned statistically only (the two-sample KS test against
 // explicit weight noise).
-#ifndef SK_NOISE_ROUNDS
-#define SK_NOISE_ROUNDS 7
-#endif
+constexpr int kNoiseRounds = 7;
 template <int ROUNDS = 10>
 __device__ __forceinline__ uint4 philox(uint4 c, uint32_t k0, uint32_t k1) {
 #pragma unroll
@@ -108,7 +106,7 @@ __device__ __forceinline__ void normals16(uint64_t seed, uint64_t call, uint32_t
                                           float k2, float z[16]) {
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
-    uint4 u = philox<SK_NOISE_ROUNDS>(make_uint4(row, (stream * 2 + (uint32_t)h) * 2 + q, (uint32_t)call,
+    uint4 u = philox<kNoiseRounds>(make_uint4(row, (stream * 2 + (uint32_t)h) * 2 + q, (uint32_t)call,
                                                  (uint32_t)(call >> 32)),
                      (uint32_t)seed, (uint32_t)(seed >> 32));
     uint32_t w[4] = {u.x, u.y, u.z, u.w};
@@ -136,7 +134,7 @@ __device__ __forceinline__ void pairs8(uint64_t seed, uint64_t call, uint32_t ro
                                        Pairs8& n) {
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
-    uint4 u = philox<SK_NOISE_ROUNDS>(make_uint4(row, (stream * 2 + (uint32_t)h) * 2 + q, (uint32_t)call,
+    uint4 u = philox<kNoiseRounds>(make_uint4(row, (stream * 2 + (uint32_t)h) * 2 + q, (uint32_t)call,
                                                  (uint32_t)(call >> 32)),
                      (uint32_t)seed, (uint32_t)(seed >> 32));
     uint32_t w[4] = {u.x, u.y, u.z, u.w};

@@ -1,6 +1,6 @@
 // sk_step.hpp — device pieces of the fused env step shared by the step
 // kernels (sk_engine.hip, sk_multi.hpp) and the self-play tick that runs the actor forward
-// in the same launch (sk_learn32.hip, k_act_step32): launch geometry, the
+// in the same launch (sk_act32.hpp, k_act_step32): launch geometry, the
 // episode counters, the device step counter, the step's argument block, the
 // replay ring insert's arrival, and k_step_split's per-lane body.
 #pragma once
@@ -498,19 +498,19 @@ __device__ __forceinline__ void split_finish(const StepArgs& a, const Cfg& c, co
 
 }  // namespace sk
 
-// k_act_step32 (csrc/sk_learn32.hip): the fp32 actor forward and k_step_split
+// k_act_step32 (csrc/sk_act32.hpp): the fp32 actor forward and k_step_split
 // in one launch, 16 games per 256-lane workgroup (sk_env_act_step)
 int sk_launch_act_step32(const float* aflat, const void* apack, float* act_out, float sd, float action_sd,
                          uint64_t seed, uint64_t* call_ctr, const sk::StepArgs& a, const sk::Cfg& c, hipStream_t st);
-// k_act_episode32 (csrc/sk_learn32.hip): the reference rule's episode, one launch
+// k_act_episode32 (csrc/sk_act32.hpp): the reference rule's episode, one launch
 int sk_launch_act_episode32(const float* aflat, const void* apack, float sd, float action_sd, uint64_t seed,
                             uint64_t* call_ctr, const sk::StepArgs& a, const sk::Cfg& c, float* states,
                             float* actions, float* rewards, int32_t* lengths, int n_ticks, hipStream_t st);
-// k_act_match32 (csrc/sk_learn32.hip): two actors' whole matches, one launch
+// k_act_match32 (csrc/sk_act32.hpp): two actors' whole matches, one launch
 int sk_launch_act_match32(const float* aflat1, const void* apack1, const float* aflat2, const void* apack2,
                           const sk::StepArgs& a, const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths,
                           int32_t* last_half, int n_ticks, hipStream_t st);
-// k_act_league32 (csrc/sk_learn32.hip): every pairing of K actors, whole matches, one launch
+// k_act_league32 (csrc/sk_act32.hpp): every pairing of K actors, whole matches, one launch
 int sk_launch_act_league32(const uint64_t* nets, int n_actors, const int32_t* pairs, int block, const sk::StepArgs& a,
                            const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
                            int n_ticks, hipStream_t st);

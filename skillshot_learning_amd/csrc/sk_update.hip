@@ -1001,16 +1001,7 @@ __device__ __forceinline__ void scatter_fwd_pack(char* out, int p, float v) {  /
   }
 }
 
-#ifndef SK_ADAM_SLICES
-#define SK_ADAM_SLICES 4
-#endif
-#ifndef SK_ADAM_PARAMS
-#define SK_ADAM_PARAMS 64
-#endif
-#ifndef SK_ADAM_INFLIGHT
-#define SK_ADAM_INFLIGHT 8
-#endif
-constexpr int kAdamParams = SK_ADAM_PARAMS, kAdamSlices = SK_ADAM_SLICES, kAdamInflight = SK_ADAM_INFLIGHT;
+constexpr int kAdamParams = 64, kAdamSlices = 4, kAdamInflight = 8;
 // partials per lane loaded in one round (k_adam_flat): 32 = the sliced fp32
 // kernels' W1 / b1 contributions at batch 256 (128 rows over 4 slices)
 constexpr int kAdamOnce = 32 + kAdamInflight;

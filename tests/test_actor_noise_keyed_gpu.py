@@ -1,5 +1,5 @@
 """The fp32 actor's exploration noise, keyed: k_actor_fwd32 / k_actor_fwd16
-(csrc/sk_learn32.hip, through ActorKernel32) against oracle/noise_ref.py, the
+(csrc/sk_act32.hpp, through ActorKernel32) against oracle/noise_ref.py, the
 numpy fp64 restatement of what they draw as a pure function of (seed, call,
 global row, unit) -- every row, both outputs, nothing masked out.
 
