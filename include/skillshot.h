@@ -332,6 +332,43 @@ int sk_env_act_league(sk_env* env, const uint64_t* nets, int32_t n_actors, const
                       int32_t block, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
                       int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, void* stream);
 
+/* The opponent-pool training tick in ONE launch (ABI 13, added: a new
+ * symbol, nothing existing changes, so SK_ABI_VERSION stays 13):
+ * sk_env_act_step's tick with sk_env_act_league's seating.  The env holds
+ * n_pairs * block games, block a multiple of 32; pairing p owns games
+ * p block .. (p + 1) block - 1, whose seat 1 acts from actor pairs[p][0] and
+ * seat 2 from actor pairs[p][1].  nets uint64[n_actors][2] and pairs
+ * int32[n_pairs][2] are DEVICE tables as sk_env_act_league's.  Actor
+ * noisy_actor (-1: nobody) is the learner: its seats draw parameter noise
+ * noise_sd and / or action noise action_sd with noise_seed and call number
+ * *call_counter + 1, keyed by their global rows of the [2N] order; every
+ * other actor acts deterministically.  Everything from acting_obs on is
+ * sk_env_act_step's: actions float[2N][2] is written, the step takes those
+ * actions, obs / reward / done / winner / obs_reset, auto_reset, the ring
+ * insert of all 2N transitions (a frozen opponent's rows are off-policy
+ * data like any other), total_copy and the episode counters.
+ * Equal, bit for bit, to these three steps: sk_actor_forward_f32 (32-row
+ * tiles, SK_FWD16=0) of every seated actor on the [2N] acting rows, the
+ * noisy actor with the sds, seed and counter above, the others without
+ * noise; each (seat, block) taking its actor's rows into actions; then
+ * sk_env_step_insert, or sk_env_step when ring is NULL.  *call_counter
+ * advances by one iff it is given and an sd is non-zero, whether or not a
+ * pairing seats the noisy actor.  A pairing whose actor index lies outside
+ * [0, n_actors), or whose actor has a null or misaligned address, is not
+ * played: its games are not stepped and none of their outputs, action or
+ * ring rows are written (the ring's total still advances by 2N).
+ * SK_EINVAL, before any launch, for a NULL table, acting_obs or actions,
+ * n_actors < 1, n_pairs < 1, block <= 0 or block % 32 != 0, an env that does
+ * not hold n_pairs * block games, noisy_actor outside [-1, n_actors), a
+ * misaligned pointer, sk_env_act_step's ring and reward_kind checks, and the
+ * CPU backend.  Stream-ordered and graph-capturable.  GPU backend only. */
+int sk_env_act_step_pool(sk_env* env, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
+                         int32_t block, int32_t noisy_actor, const float* acting_obs, float* actions, float noise_sd,
+                         float action_sd, uint64_t noise_seed, uint64_t* call_counter, float* obs, float* reward,
+                         int32_t reward_kind, uint8_t* done, uint8_t* winner, int32_t tick_limit, int32_t auto_reset,
+                         int32_t random_positions, float* obs_reset, float* ring, int64_t capacity, int64_t* total,
+                         uint32_t* arrivals, int64_t* total_copy, void* stream);
+
 /* sk_env_act_step prepared, not launched (ABI 8): the same arguments
  * (N % 4 == 0, ring given or not) into *job, and the env advances its step
  * slot as if the launch had been issued.  The job is then run, exactly once

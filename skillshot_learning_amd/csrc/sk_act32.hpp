@@ -17,6 +17,9 @@
 //   k_episode_finish the counters' advance by the ticks played
 //   k_act_match32    two actors play whole matches in one launch
 //   k_act_league32   every pairing of K actors in one launch
+//   k_act_step_pool32  the opponent-pool training tick: each block of games
+//                    acts from the two actors its pairing names, one of them
+//                    the noisy learner, then steps and inserts as k_act_step32
 //   k_split_pack32   the actor's split pack from its flat fp32 parameters
 // and, at the end, their host launchers (sk_launch_act_*, declared in
 // sk_step.hpp and called by sk_engine.hip and sk_learn32.hip) and C entry
@@ -196,6 +199,13 @@ struct RowsSeat {
   __device__ int64_t operator()(int i) const { return base + g0 + i; }
   __device__ bool valid(int i) const { return g0 + i < n; }
 };
+// The same seat where the actions are wanted in `out` as well (the pool tick,
+// k_act_step_pool32: actions float[2N][2] as sk_env_act_step writes them).
+// With N % 32 == 0 every aligned 4-row group of a seat's rows is one of the
+// contiguous map's, so the noise drawn for a row is k_actor_fwd32's.
+struct RowsSeatStore : RowsSeat {
+  static constexpr bool kStore = true;
+};
 
 // one 32-row tile per workgroup of 4 waves: layer 1 n-tiles w, 4 + w,
 // layer 2 n-tile w, layer 3 by all threads.  NOISE: per layer y = xW + b +
@@ -223,8 +233,11 @@ struct RowsSeat {
 // two: it held every loop-invariant weight fragment of the tile across the
 // episode (512 VGPRs, one workgroup per CU, spills) until its weight
 // addresses were made opaque per tick (180 -> 110 us per tick,
-// profiles/r04o_episode_ab.jsonl)
-constexpr int kActWaves = 3, kEpisodeWaves = 2;
+// profiles/r04o_episode_ab.jsonl).  The pool tick at two: with a noisy and
+// a plain tile behind a branch and wave 0's step lanes live across both it
+// spills 136 VGPRs at three waves and 26 at two (the compiler's resource
+// report)
+constexpr int kActWaves = 3, kEpisodeWaves = 2, kPoolWaves = 2;
 constexpr int kLdX1 = 24, kLdX2 = 136;              // bf16 row strides (48 / 272 B: conflict-free 16-B reads)
 constexpr int kX1Plane = 32 * kLdX1, kX2Plane = 32 * kLdX2;  // kX2Plane: one half of layer 1's units
 constexpr size_t kActorTileLds = (size_t)(4 * kX1Plane + 4 * kX2Plane) * 2;
@@ -678,6 +691,93 @@ __global__ void __launch_bounds__(kFwdThreads, kEpisodeWaves) k_act_league32(Lea
   match_ticks32((const float*)f1, (const char*)k1, (const float*)f2, (const char*)k2, a, c, mt, (char*)smem_sl);
 }
 
+// The opponent-pool training tick (sk_env_act_step_pool): k_act_step32's tick
+// with k_act_league32's seating.  Workgroup b owns games 32b .. 32b + 31 and
+// plays pairing p = b / (block / 32): pairs[p] and those actors' rows of nets
+// are read once with uniform loads, under the league's guard.  One tick per
+// launch: split_load for wave 0's 64 (game, player) lanes first (the state
+// and ring-source loads fly under both MFMA chains), the tile on the 32
+// seat-1 rows from net pairs[p][0], the tile on the 32 seat-2 rows from net
+// pairs[p][1] (RowsSeatStore: actions to `act_out` and to sAct), then
+// split_finish with the caller's full StepArgs: obs, reward, done, winner,
+// auto-reset, obs_reset, the ring insert, the episode counters into slot
+// line b.  A seat draws noise iff its actor is `noisy_actor`: parameter
+// noise through actor_tile32<true> when sd != 0, action noise by action_sd,
+// both with call number call_ctr[0] + 1 and keyed by the global row of the
+// [2N] order; every other seat is actor_tile32<false> with action_sd 0.
+// Whether a seat is noisy is workgroup-uniform; the seat loop is kept rolled
+// so the kernel holds one inlined tile of each kind.  LDS between the two
+// tiles: as match_ticks32's.  The launch advances the call number once
+// (advance_call32 over the whole grid) iff it was given and an sd is
+// non-zero, whoever is seated.  A guarded workgroup (pair index outside
+// [0, K), a null or misaligned address) runs no tile and clears `in` of all
+// its lanes: its games are not stepped and nothing of theirs is written, but
+// it still advances the step slot (workgroup 0) and arrives for the ring and
+// the call number.  Equal, bit for bit, to sk_actor_forward_f32 (32-row
+// tiles) of every seated actor on the [2N] rows, each (seat, block) taking
+// its actor's rows, followed by sk_env_step(_insert).
+struct PoolArgs {
+  const uint64_t* nets;  // [K][2]
+  const int32_t* pairs;  // [P][2]
+  int n_actors;
+  int wgs_per_pair;      // block / 32
+  int noisy_actor;       // -1: nobody
+};
+constexpr size_t kActPoolLds = kActorTileLds + 64 * sizeof(float2);
+__global__ void __launch_bounds__(kFwdThreads, kPoolWaves) k_act_step_pool32(PoolArgs pl, float* __restrict__ act_out,
+                                                                             float sd, float action_sd, uint64_t seed,
+                                                                             uint64_t* __restrict__ call_ctr,
+                                                                             sk::StepArgs a, sk::Cfg c) {
+  extern __shared__ __attribute__((aligned(16))) float smem_sl[];
+  char* smem = (char*)smem_sl;
+  float2* sAct = (float2*)(smem + kActorTileLds);
+  const int lane = threadIdx.x & 63;
+  const bool w0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0;
+  const int64_t g0 = (int64_t)blockIdx.x * 32;
+  sk_counters* slot = a.ctr ? a.ctr + (size_t)blockIdx.x * SK_CTR_STRIDE : nullptr;
+  const int p = (int)blockIdx.x / pl.wgs_per_pair;
+  const int i1 = pl.pairs[2 * p], i2 = pl.pairs[2 * p + 1];
+  uint64_t f1 = 0, k1 = 0, f2 = 0, k2 = 0;
+  if ((unsigned)i1 < (unsigned)pl.n_actors && (unsigned)i2 < (unsigned)pl.n_actors) {
+    f1 = pl.nets[2 * i1];
+    k1 = pl.nets[2 * i1 + 1];
+    f2 = pl.nets[2 * i2];
+    k2 = pl.nets[2 * i2 + 1];
+  }
+  const bool ok = f1 && k1 && f2 && k2 && !((f1 | f2) & 3) && !((k1 | k2) & 15);
+  sk::StepLane L;
+  if (w0) {
+    L = sk::split_load(a, 2 * g0 + lane, slot);
+    if (!ok) L.in = false;
+  }
+  const bool draws = (sd != 0.f || action_sd != 0.f) && call_ctr;
+  const uint64_t call = draws ? call_ctr[0] + 1 : 0;
+  if (ok) {
+#pragma unroll 1
+    for (int seat = 0; seat < 2; ++seat) {
+      const float* af = (const float*)(seat ? f2 : f1);
+      const char* ap = (const char*)(seat ? k2 : k1);
+      const bool noisy = (seat ? i2 : i1) == pl.noisy_actor;
+      RowsSeatStore R;
+      R.base = seat ? a.n : 0;
+      R.g0 = g0;
+      R.n = a.n;
+      if (noisy && sd != 0.f)
+        actor_tile32<true>(net_of(af, kALd, 2), ap, a.acting_obs, act_out, R, sd, action_sd, seed, call,
+                           actor_lds(smem), sAct + 32 * seat);
+      else
+        actor_tile32<false>(net_of(af, kALd, 2), ap, a.acting_obs, act_out, R, 0.f, noisy ? action_sd : 0.f, seed,
+                            call, actor_lds(smem), sAct + 32 * seat);
+    }
+  }
+  __syncthreads();
+  if (w0) sk::split_finish(a, c, L, ok ? sAct[(lane & 1) * 32 + (lane >> 1)] : make_float2(0.f, 0.f), slot);
+  if (draws) {
+    __syncthreads();
+    advance_call32(call_ctr, call, gridDim.x);
+  }
+}
+
 // ---------------------------------------------------------------- actor forward, 16-row tiles
 // The same forward for small row counts: a 32-row tile is a serial chain of
 // load latencies around 3.4 us of MFMA per workgroup (9.4 us at 256 rows);
@@ -942,6 +1042,24 @@ int sk_launch_act_league32(const uint64_t* nets, int n_actors, const int32_t* pa
   k_act_league32<<<G, kFwdThreads, kActMatchLds, st>>>(lg, a, c, mt);
   if (hipGetLastError() != hipSuccess) return SK_EHIP;
   k_episode_finish<<<1, 256, 0, st>>>(lengths, a.n, a.step, nullptr);
+  return hipGetLastError() == hipSuccess ? SK_OK : SK_EHIP;
+}
+
+// the opponent-pool training tick (sk_env_act_step_pool, csrc/sk_engine.hip): a.n = n_pairs * block,
+// block % 32 == 0; nets / pairs are device tables
+int sk_launch_act_step_pool32(const uint64_t* nets, int n_actors, const int32_t* pairs, int block, int noisy_actor,
+                              float* act_out, float sd, float action_sd, uint64_t seed, uint64_t* call_ctr,
+                              const sk::StepArgs& a, const sk::Cfg& c, hipStream_t st) {
+  static bool attr = false;
+  if (!attr) {
+    set_lds32(k_act_step_pool32, kActPoolLds);
+    attr = true;
+  }
+  if (!nets || !pairs || !act_out || n_actors < 1 || block <= 0 || block % 32 || a.n % block) return SK_EINVAL;
+  if (noisy_actor < -1 || noisy_actor >= n_actors) return SK_EINVAL;
+  const unsigned G = (unsigned)(a.n / 32);
+  const PoolArgs pl{nets, pairs, n_actors, block / 32, noisy_actor};
+  k_act_step_pool32<<<G, kFwdThreads, kActPoolLds, st>>>(pl, act_out, sd, action_sd, seed, call_ctr, a, c);
   return hipGetLastError() == hipSuccess ? SK_OK : SK_EHIP;
 }
 

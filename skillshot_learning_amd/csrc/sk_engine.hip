@@ -1227,6 +1227,36 @@ int sk_env_act_league(sk_env* e, const uint64_t* nets, int32_t n_actors, const i
   return SK_OK;
 }
 
+int sk_env_act_step_pool(sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
+                         int32_t block, int32_t noisy_actor, const float* acting_obs, float* actions, float noise_sd,
+                         float action_sd, uint64_t noise_seed, uint64_t* call_counter, float* obs, float* reward,
+                         int32_t reward_kind, uint8_t* done, uint8_t* winner, int32_t tick_limit, int32_t auto_reset,
+                         int32_t random_positions, float* obs_reset, float* ring, int64_t capacity, int64_t* total,
+                         uint32_t* arrivals, int64_t* total_copy, void* stream) {
+  SK_CHECK_ENV(e);
+  if (!nets || !pairs) return fail(SK_EINVAL, "the nets or the pairs table is NULL");
+  if (!acting_obs || !actions) return fail(SK_EINVAL, "acting_obs / actions is NULL");
+  if (n_actors < 1 || n_pairs < 1) return fail(SK_EINVAL, "n_actors and n_pairs must be at least 1");
+  if (block <= 0 || block % 32) return fail(SK_EINVAL, "block must be a positive multiple of 32");
+  if ((int64_t)e->n != (int64_t)n_pairs * block) return fail(SK_EINVAL, "the env must hold n_pairs * block games");
+  if (noisy_actor < -1 || noisy_actor >= n_actors) return fail(SK_EINVAL, "noisy_actor must lie in [-1, n_actors)");
+  if ((((uintptr_t)nets) & 7) || (((uintptr_t)pairs) & 3))
+    return fail(SK_EINVAL, "nets must be 8-byte aligned, pairs 4-byte");
+  if ((((uintptr_t)actions) & 7) || (((uintptr_t)acting_obs) & 15))
+    return fail(SK_EINVAL, "actions must be 8-byte aligned, acting_obs 16-byte");
+  if (((uintptr_t)call_counter) & 7) return fail(SK_EINVAL, "call_counter must be 8-byte aligned");
+  StepArgs a;
+  int rc = act_step_args(e, acting_obs, actions, obs, reward, reward_kind, done, winner, tick_limit, auto_reset,
+                         random_positions, obs_reset, ring, capacity, total, arrivals, total_copy, a);
+  if (rc != SK_OK) return rc;
+  if (e->host) return fail(SK_EINVAL, "sk_env_act_step_pool runs on the GPU backend");
+  rc = sk_launch_act_step_pool32(nets, n_actors, pairs, block, noisy_actor, actions, noise_sd, action_sd, noise_seed,
+                                 call_counter, a, e->dcfg, (hipStream_t)stream);
+  if (rc != SK_OK) return fail(rc, "k_act_step_pool32 launch failed");
+  e->parity ^= 1;
+  return SK_OK;
+}
+
 static_assert(sizeof(ActStepJob) <= sizeof(sk_step_job), "sk_step_job too small for ActStepJob");
 
 int sk_env_act_step_job(sk_env* e, const float* actor_flat, const void* actor_pack, const float* acting_obs,

@@ -514,3 +514,7 @@ int sk_launch_act_match32(const float* aflat1, const void* apack1, const float* 
 int sk_launch_act_league32(const uint64_t* nets, int n_actors, const int32_t* pairs, int block, const sk::StepArgs& a,
                            const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
                            int n_ticks, hipStream_t st);
+// k_act_step_pool32 (csrc/sk_act32.hpp): the pool training tick, each block of games acting from its pairing's actors
+int sk_launch_act_step_pool32(const uint64_t* nets, int n_actors, const int32_t* pairs, int block, int noisy_actor,
+                              float* act_out, float sd, float action_sd, uint64_t seed, uint64_t* call_ctr,
+                              const sk::StepArgs& a, const sk::Cfg& c, hipStream_t st);

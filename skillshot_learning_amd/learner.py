@@ -877,6 +877,24 @@ def bradley_terry_elo(score, n):
     return 400.0 * np.log10(p)
 
 
+def pool_pairs(n_envs, n_opponents, self_play=0):
+    """The seating of SkillshotLearner.train_vs: one (seat-1 actor, seat-2
+    actor) pair per block of 32 games, n_envs / 32 entries, actor 0 the
+    learner and actor k the k-th opponent.  The blocks cycle through (0, k),
+    (k, 0) for k = 1 .. n_opponents (both seatings: player 1 is hit-tested
+    first, check_collision, SkillshotGame.py:58-94) and, after every full
+    cycle, `self_play` blocks of (0, 0)."""
+    n, K, sp = int(n_envs), int(n_opponents), int(self_play)
+    if K < 1 or sp < 0:
+        raise ValueError("pool_pairs needs at least one opponent and self_play >= 0")
+    if n <= 0 or n % 32:
+        raise ValueError("n_envs must be a positive multiple of 32 (one pairing per 32 games)")
+    if n // 32 < 2 * K:
+        raise ValueError(f"{n // 32} blocks of 32 games do not hold one cycle of {2 * K} pairings")
+    cycle = [pr for k in range(1, K + 1) for pr in ((0, k), (k, 0))] + [(0, 0)] * sp
+    return [cycle[b % len(cycle)] for b in range(n // 32)]
+
+
 class SkillshotLearner:
     """Batched self-play DDPG learner (SkillshotLearner.py:13-682 API shape).
 
@@ -1474,6 +1492,85 @@ class SkillshotLearner:
             if self.replay.size >= warmup:
                 for _ in range(updates_per_tick):
                     # the fused path returns slots of a loss ring: keep copies
+                    stats.append(tuple(x.detach().clone() for x in self.replay_update(batch)))
+            self._refresh_actor_pack()
+        return stats
+
+    def train_vs(self, opponents, n_ticks, batch=256, updates_per_tick=1, warmup=None, self_play=0):
+        """train_ticks against a pool of frozen opponents: the learner, with
+        its exploration noise, sits in one seat of every game and a frozen,
+        deterministic opponent in the other (both seats in `self_play`
+        blocks per cycle), and all 2N transitions of every tick enter the
+        replay ring (an opponent's rows are off-policy data like any other).
+
+        opponents  a list of what evaluate takes as `opponent`: an Actor, an
+                   actor state_dict, another SkillshotLearner, a checkpoint
+                   index, or None (the learner's current actor, without
+                   noise).  Their weights are read at the call, into nets of
+                   train_vs's own (held until the next call); they are never
+                   written.
+        The games are seated by pool_pairs(n_envs, len(opponents), self_play)
+        in blocks of 32: n_envs must be a multiple of 32 with at least two
+        blocks per opponent.
+
+        Each tick is one pool tick, then, once the ring holds `warmup` rows
+        (default `batch`), `updates_per_tick` replay updates, exactly as
+        train_ticks; returns its stats list.  With the fp32 acting kernel on
+        a GPU the pool tick is ONE launch (VecSkillshotGame.act_step_pool);
+        otherwise, or with SK_POOL_KERNEL=0, every actor's forward on the
+        whole observation, a select by (seat, block), step and replay.add, on
+        either backend.  The training env, its step counter and the noise
+        call numbers carry on: train_ticks and train_vs calls can be mixed."""
+        try:
+            entries = list(opponents)
+        except TypeError:
+            raise TypeError("opponents must be a list of actors")
+        if not entries:
+            raise ValueError("train_vs needs at least one opponent")
+        g = self.game_environment
+        pairs = pool_pairs(self.n_envs, len(entries), self_play)
+        used = {}
+        players = [self._match_actor(e, cache=self.__dict__.setdefault("_pool_actors", {}), used=used)
+                   for e in entries]
+        self._pool_actors = used  # this call's nets stay, earlier calls' go
+        use_kernel = (self._match_kernel_usable() and all(p[1] is not None for p in players) and
+                      os.environ.get("SK_POOL_KERNEL", "1") != "0")
+        mode = self.exploration
+        warmup = batch if warmup is None else warmup
+        obs = self.prepare_states()
+        stats = []
+        if use_kernel:
+            kernels = [self.actor_kernel] + [p[1] for p in players]
+            res, resets = None, [None, None]
+        else:
+            # seat[p, i]: the actor of player p + 1 of game i
+            seat = torch.tensor(pairs, dtype=torch.int64, device=self.device).t().repeat_interleave(32, dim=1)
+        for t in range(n_ticks):
+            if use_kernel:
+                # the launch reads obs while it writes obs_reset: two buffers, taken in turn
+                o = dict(res) if res is not None else {}
+                o["obs_reset"] = resets[t & 1]
+                res = g.act_step_pool(kernels, pairs, 32, obs, noisy=0,
+                                      noise_sd=self.param_noise_sd if mode == "param_noise" else 0.0,
+                                      action_sd=self.action_noise_sd if mode == "action_noise" else 0.0,
+                                      ring=self.replay, reward="looking", auto_reset=True, reset_obs=True, out=o)
+                resets[t & 1] = obs = res["obs_reset"]
+                pairs = res["tables"][1]  # the checked seating: not walked again next tick
+            else:
+                with torch.no_grad():
+                    act = self.model_act(obs)
+                    x = obs.reshape(-1, STATE_DIM)
+                    for k, (fwd, _) in enumerate(players):
+                        a = fwd(x).reshape(2, -1, ACTION_DIM)
+                        act = torch.where((seat == k + 1)[:, :, None], a, act)
+                    act = act.contiguous()
+                out = self.do_actions(act, reset_obs=True)
+                d = out["done"].float().repeat(2)
+                self.replay.add(obs.reshape(-1, STATE_DIM), act.reshape(-1, ACTION_DIM), out["reward"].reshape(-1),
+                                out["obs"].reshape(-1, STATE_DIM), d)
+                obs = out["obs_reset"]
+            if self.replay.size >= warmup:
+                for _ in range(updates_per_tick):
                     stats.append(tuple(x.detach().clone() for x in self.replay_update(batch)))
             self._refresh_actor_pack()
         return stats

@@ -467,6 +467,49 @@ class VecSkillshotGame:
                                          _ptr(actor._ctr), REWARD_KINDS[reward], self.tick_limit, self._stream()))
         return dict(states=st[:T + 1], actions=ac[:T], rewards=rw[:T], lengths=ln)
 
+    def _seating(self, what, actors, pairs, block, o):
+        """act_league's / act_step_pool's host check of a seating: (actors,
+        the pairs as a tuple of int pairs, block).  `pairs` that is the very
+        tuple an earlier call checked and returned (o["tables"][1], `o` that
+        call's dict) for as many actors is taken as checked: a per-tick
+        caller does not walk thousands of pairs again."""
+        actors = list(actors)
+        block = int(block)
+        known = o.get("tables")
+        if (known is not None and pairs is known[1] and len(known[0]) == len(actors) and
+                len(pairs) * block == self.n and block > 0 and block % 32 == 0):
+            return actors, pairs, block
+        try:
+            plist = tuple((int(i), int(j)) for i, j in pairs)
+        except (TypeError, ValueError):
+            raise ValueError("pairs must be a list of (seat-1 actor, seat-2 actor) index pairs")
+        if not actors or not plist:
+            raise ValueError(f"{what} needs at least one actor and one pairing")
+        if not all(hasattr(a, "flat") and hasattr(a, "ensure_pack") for a in actors):
+            raise TypeError("actors must be ActorKernel32 objects (the fp32 actor with its split pack)")
+        if block <= 0 or block % 32:
+            raise ValueError("block must be a positive multiple of 32")
+        if len(plist) * block != self.n:
+            raise ValueError(f"the env holds {self.n} games, not len(pairs) * block = {len(plist) * block}")
+        for i, j in plist:
+            if not (0 <= i < len(actors) and 0 <= j < len(actors)):
+                raise ValueError(f"pair ({i}, {j}) names an actor outside [0, {len(actors)})")
+        return actors, plist, block
+
+    @staticmethod
+    def _seating_tables(actors, plist, o, buf):
+        """the two device tables of a seating (the actors' addresses, the
+        pairs), taken from the dict `o` of an earlier call and uploaded only
+        when the actors' buffers or the pairs differ from that call's:
+        (nets, pairs, the key to keep as `tables`)"""
+        addr = tuple((a.flat.data_ptr(), a.ensure_pack().data_ptr()) for a in actors)
+        nets = buf("nets", (len(actors), 2), torch.int64)
+        prs = buf("pairs", (len(plist), 2), torch.int32)
+        if o.get("tables") != (addr, plist) or nets is not o.get("nets") or prs is not o.get("pairs"):
+            nets.copy_(torch.tensor(addr, dtype=torch.int64))
+            prs.copy_(torch.tensor(plist, dtype=torch.int32))
+        return nets, prs, (addr, plist)
+
     def act_match(self, actor1, actor2, start_obs, n_ticks=None, reward="looking", out=None, resume=False):
         """Two actors play every game head to head in ONE launch
         (sk_env_act_match; the loop of SkillshotLearner.py:302-318 with two
@@ -537,25 +580,9 @@ class VecSkillshotGame:
         and uploads nothing."""
         if self.is_cpu:
             raise SkillshotError("act_league runs on the GPU backend (SkillshotLearner.league loops on the CPU one)")
-        actors = list(actors)
-        block = int(block)
-        try:
-            plist = tuple((int(i), int(j)) for i, j in pairs)
-        except (TypeError, ValueError):
-            raise ValueError("pairs must be a list of (seat-1 actor, seat-2 actor) index pairs")
-        if not actors or not plist:
-            raise ValueError("act_league needs at least one actor and one pairing")
-        if not all(hasattr(a, "flat") and hasattr(a, "ensure_pack") for a in actors):
-            raise TypeError("actors must be ActorKernel32 objects (the fp32 actor with its split pack)")
-        if block <= 0 or block % 32:
-            raise ValueError("block must be a positive multiple of 32")
-        if len(plist) * block != self.n:
-            raise ValueError(f"the env holds {self.n} games, not len(pairs) * block = {len(plist) * block}")
-        for i, j in plist:
-            if not (0 <= i < len(actors) and 0 <= j < len(actors)):
-                raise ValueError(f"pair ({i}, {j}) names an actor outside [0, {len(actors)})")
-        T = int(self.tick_limit if n_ticks is None else n_ticks)
         o = out or {}
+        actors, plist, block = self._seating("act_league", actors, pairs, block, o)
+        T = int(self.tick_limit if n_ticks is None else n_ticks)
         if resume and (o.get("returns") is None or o.get("lengths") is None):
             raise ValueError("resume needs the dict a previous act_league returned as out")
 
@@ -567,12 +594,7 @@ class VecSkillshotGame:
                 raise ValueError(f"out[{key!r}] must be contiguous {dtype} {shape} on {self.device}")
             return t
 
-        addr = tuple((a.flat.data_ptr(), a.ensure_pack().data_ptr()) for a in actors)
-        nets = buf("nets", (len(actors), 2), torch.int64)
-        prs = buf("pairs", (len(plist), 2), torch.int32)
-        if o.get("tables") != (addr, plist) or nets is not o.get("nets") or prs is not o.get("pairs"):
-            nets.copy_(torch.tensor(addr, dtype=torch.int64))
-            prs.copy_(torch.tensor(plist, dtype=torch.int32))
+        nets, prs, tables = self._seating_tables(actors, plist, o, buf)
         start = start_obs.reshape(2, self.n, 12)  # (may be out["obs"]: read before it is rewritten)
         obs2 = buf("obs2", (2, 2, self.n, 12), torch.float32)
         ret = buf("returns", (2, self.n), torch.float32)
@@ -591,7 +613,71 @@ class VecSkillshotGame:
         else:
             total.copy_(call_ln)
         return dict(lengths=total, returns=ret, obs=obs, obs2=obs2, call_lengths=call_ln,
-                    last_half=o.get("last_half"), nets=nets, pairs=prs, tables=(addr, plist))
+                    last_half=o.get("last_half"), nets=nets, pairs=prs, tables=tables)
+
+    def act_step_pool(self, actors, pairs, block, acting_obs, noisy=None, noise_sd=0.0, action_sd=0.0, ring=None,
+                      reward="looking", auto_reset=True, reset_obs=True, out=None, actions=None, total_copy=None):
+        """The opponent-pool training tick in ONE launch
+        (sk_env_act_step_pool): act_step's tick with act_league's seating.
+        The env holds len(pairs) blocks of `block` games (a multiple of 32);
+        in block p seat 1 acts from actors[pairs[p][0]] and seat 2 from
+        actors[pairs[p][1]] (`actors` a list of ActorKernel32, `pairs` a host
+        list of (i, j)).  `noisy` (an index into actors, or None) is the
+        learner: its seats draw parameter noise noise_sd and / or action
+        noise action_sd with that actor's seed and noise call number, which
+        the launch advances; every other actor acts deterministically and
+        its call number stays.  Equal, bit for bit, to every seated actor's
+        forward (32-row tiles) on acting_obs [2, N, 12], each (seat, block)
+        taking its actor's rows, followed by step_insert (ring given: all 2N
+        transitions enter it; total_copy as step_insert's) or step.  The two
+        device tables are kept in the returned dict (`nets`, `pairs`) and
+        uploaded again only when the actors' buffers or `pairs` differ from
+        the call that made them (out=); a per-tick caller passes the checked
+        pairs back as well (pairs=out["tables"][1]) and skips the host's walk
+        over them.  Returns act_step's dict."""
+        if self.is_cpu:
+            raise SkillshotError("act_step_pool runs on the GPU backend (SkillshotLearner.train_vs loops on the CPU one)")
+        o = out or {}
+        actors, plist, block = self._seating("act_step_pool", actors, pairs, block, o)
+        if noisy is not None and (isinstance(noisy, bool) or not 0 <= int(noisy) < len(actors)):
+            raise ValueError(f"noisy must be None or an actor index in [0, {len(actors)})")
+        if noisy is None and (noise_sd != 0.0 or action_sd != 0.0):
+            raise ValueError("noise_sd / action_sd need the noisy actor's index")
+
+        def buf(key, shape, dtype):
+            t = o.get(key)
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=self.device)
+            elif tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"out[{key!r}] must be contiguous {dtype} {shape} on {self.device}")
+            return t
+
+        nets, prs, tables = self._seating_tables(actors, plist, o, buf)
+        obs_t = o.get("obs") if o.get("obs") is not None else self.new_obs()
+        rew_t = o.get("reward") if o.get("reward") is not None else torch.empty((2, self.n), dtype=torch.float32,
+                                                                                device=self.device)
+        done = o.get("done") if o.get("done") is not None else torch.empty(self.n, dtype=torch.uint8,
+                                                                            device=self.device)
+        win = o.get("winner") if o.get("winner") is not None else torch.empty(self.n, dtype=torch.uint8,
+                                                                               device=self.device)
+        obs_r = (o.get("obs_reset") if o.get("obs_reset") is not None else self.new_obs()) if reset_obs else None
+        act = actions if actions is not None else torch.empty((2, self.n, 2), dtype=torch.float32, device=self.device)
+        s = acting_obs.float().contiguous()
+        if s.numel() != 2 * self.n * 12 or act.numel() != 4 * self.n or not act.is_contiguous():
+            raise ValueError("acting_obs must hold [2, N, 12] floats, actions [2, N, 2] (contiguous)")
+        ring_args = ((_ptr(ring.buf), ring.cap, _ptr(ring.total_t), _ptr(ring.arrivals()), _ptr(total_copy))
+                     if ring is not None else (None, 0, None, None, None))
+        learner = actors[int(noisy)] if noisy is not None else None
+        check(self._L.sk_env_act_step_pool(
+            self._h, _ptr(nets), len(actors), _ptr(prs), len(plist), block, -1 if noisy is None else int(noisy),
+            _ptr(s), _ptr(act), float(noise_sd), float(action_sd), learner.seed if learner is not None else 0,
+            _ptr(learner._ctr) if learner is not None else None, _ptr(obs_t), _ptr(rew_t), REWARD_KINDS[reward],
+            _ptr(done), _ptr(win), self.tick_limit, int(bool(auto_reset)), int(self.random_positions), _ptr(obs_r),
+            *ring_args, self._stream()))
+        if ring is not None:
+            ring.total += 2 * self.n  # host mirror
+        return dict(obs=obs_t, reward=rew_t, done=done, winner=win, obs_reset=obs_r, actions=act, nets=nets,
+                    pairs=prs, tables=tables)
 
     def step_raw(self, actions_ptr, done_ptr=None, obs_ptr=None, reward_ptr=None, winner_ptr=None,
                  auto_reset=True, stream=None):
