@@ -332,6 +332,50 @@ int sk_env_act_league(sk_env* env, const uint64_t* nets, int32_t n_actors, const
                       int32_t block, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
                       int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, void* stream);
 
+/* The match record (ABI 13, added: new symbols, nothing existing changes, so
+ * SK_ABI_VERSION stays 13): sk_env_act_match_rec / sk_env_act_league_rec are
+ * sk_env_act_match / sk_env_act_league, every argument before `rec` theirs,
+ * and keep what the first per_block games of every block of games did at each
+ * tick.  A match is one block of the env's N games; a league's blocks are its
+ * pairings.  Game i, with b = i / block and k = i % block, is recorded iff
+ * k < per_block, as row j = b per_block + k; rows = blocks * per_block.
+ * states holds `slabs` slabs of `rows` states in the engine's plane layout
+ * (n_envs = slabs * rows): state (s, j) is game s * rows + j of each plane.
+ * Let c be the ticks a recorded game plays in this call.  For c >= 1 the call
+ * writes, for t = 0 .. c - 1, the game's state before the call's tick t to
+ * slab slab0 + t, the float2 (speed, look) that seat p + 1 acted with at that
+ * tick, unclamped, to actions[slab0 + t][p][j], and the seat's reward of the
+ * tick to rewards[slab0 + t][p][j] (rewards nullable; it needs `returns`, the
+ * launch computes no reward without it); and the state after the game's last
+ * tick of the call to slab slab0 + c.  Nothing past slab slab0 + c of a row
+ * is written, and a game that plays no tick in the call (ended before it, a
+ * league's pad game, a pairing the league's guard refuses) writes nothing.
+ * A match continued in a later call passes slab0 = the ticks the earlier
+ * calls ran: a game's slab slab0 is then rewritten with the same state.
+ * Everything else the call does is, bit for bit, what its plain twin does:
+ * planes, obs2, returns, lengths, last_half, the step counter; neither
+ * actor's noise call number moves.
+ * SK_EINVAL with a message, before any launch, for everything the plain twin
+ * refuses, a NULL rec, plane or actions, per_block < 1 or above the block,
+ * rows != blocks * per_block, states.n_envs != slabs * rows, slab0 < 0,
+ * slab0 + n_ticks + 1 > slabs, rewards without returns, a misaligned pointer
+ * (8 bytes for the planes, 4 bytes for actions and rewards), and the CPU
+ * backend.  Stream-ordered and graph-capturable.  GPU backend only. */
+typedef struct sk_match_record {
+  sk_state_view states;   /* n_envs = slabs * rows; device planes */
+  float* actions;         /* [slabs - 1][2][rows][2] */
+  float* rewards;         /* [slabs - 1][2][rows], nullable */
+  int32_t slabs, rows, per_block, slab0;
+} sk_match_record;
+int sk_env_act_match_rec(sk_env* env, const float* actor1_flat, const void* actor1_pack, const float* actor2_flat,
+                         const void* actor2_pack, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
+                         int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, const sk_match_record* rec,
+                         void* stream);
+int sk_env_act_league_rec(sk_env* env, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
+                          int32_t block, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
+                          int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, const sk_match_record* rec,
+                          void* stream);
+
 /* The opponent-pool training tick in ONE launch (ABI 13, added: a new
  * symbol, nothing existing changes, so SK_ABI_VERSION stays 13):
  * sk_env_act_step's tick with sk_env_act_league's seating.  The env holds

@@ -17,6 +17,9 @@
 //   k_episode_finish the counters' advance by the ticks played
 //   k_act_match32    two actors play whole matches in one launch
 //   k_act_league32   every pairing of K actors in one launch
+//   k_act_match32_rec, k_act_league32_rec  the same two, keeping each tick's
+//                    state, actions and rewards of the first games of every
+//                    block (the match record)
 //   k_act_step_pool32  the opponent-pool training tick: each block of games
 //                    acts from the two actors its pairing names, one of them
 //                    the noisy learner, then steps and inserts as k_act_step32
@@ -588,12 +591,53 @@ struct MatchArgs {
   int n_ticks;
 };
 constexpr size_t kActMatchLds = kActorTileLds + 64 * sizeof(float2) + 16;
+// The match record (sk_env_act_match_rec / sk_env_act_league_rec, DESIGN
+// §18): the recording instantiations (REC) keep, for the first per_block
+// games of every block of games, each tick's pre-tick state, both seats'
+// actions and rewards, and the state after the game's last tick of the call.
+// Game k < per_block of block b is row j = b per_block + k; state (s, j) lies
+// at index s rows + j of each plane (the engine's layout, `rows` games per
+// slab), the action and the reward of seat p + 1 at tick t at [(slab0 + t) 2
+// + p] rows + j.  A game that plays c >= 1 ticks of the call writes slabs
+// slab0 .. slab0 + c of its row and nothing past them; one that plays none
+// writes nothing.  The pre-tick state is what split_load just loaded, the
+// action what the lane hands to split_finish, the reward what the lane reads
+// back for its return: plain vector stores of values already in registers.
+struct RecArgs {
+  int2* pos;
+  double* rot;
+  int2* qpos;
+  double* qrot;
+  int2* qcdage;
+  int2* misc;
+  float* actions;   // [slabs - 1][2][rows][2]
+  float* rewards;   // [slabs - 1][2][rows] (nullable)
+  int64_t rows;
+  int per_block, slab0;
+  int wgs_per_block;  // the league's block / 32 (a match is one block of N games: unused)
+};
+// one state of a recorded row: this (game, player) lane's half of the five
+// player planes, and misc from the player-1 lane
+__device__ __forceinline__ void rec_state(const RecArgs& rc, int64_t at, int p, int2 pp, double rot, int2 qq,
+                                          double qrot, int2 ca, int2 mi) {
+  const int64_t h = 2 * at + p;
+  rc.pos[h] = pp;
+  rc.rot[h] = rot;
+  rc.qpos[h] = qq;
+  rc.qrot[h] = qrot;
+  rc.qcdage[h] = ca;
+  if (p == 0) rc.misc[at] = mi;
+}
 // match_ticks32: a workgroup's matches from the first tick to the last, on
 // the LDS at `smem` (kActMatchLds bytes).  k_act_match32 runs it on its
-// arguments, k_act_league32 on the two actors its pairing names.
+// arguments, k_act_league32 on the two actors its pairing names.  REC (the
+// _rec kernels): the workgroup's games are games rec_k0 .. rec_k0 + 31 of
+// block rec_b of the record `rc`; every line of it is under if constexpr.
+template <bool REC>
 __device__ __forceinline__ void match_ticks32(const float* aflat1, const char* apack1, const float* aflat2,
                                               const char* apack2, const sk::StepArgs& a, const sk::Cfg& c,
-                                              const MatchArgs& mt, char* smem) {
+                                              const MatchArgs& mt, char* smem, const RecArgs* rc = nullptr,
+                                              int rec_b = 0, int rec_k0 = 0) {
   float2* sAct = (float2*)(smem + kActorTileLds);
   int* sAlive = (int*)(sAct + 64);
   const int lane = threadIdx.x & 63;
@@ -606,6 +650,16 @@ __device__ __forceinline__ void match_ticks32(const float* aflat1, const char* a
   float acc = ret ? *ret : 0.f;
   if (mine && (lane & 1) == 0) mt.lengths[gi] = 0;
   if (blockIdx.x == 0 && threadIdx.x == 0 && mt.last_half) *mt.last_half = mt.n_ticks & 1;
+  // the record: whether the workgroup records at all is uniform (its first
+  // game's k), whether a lane does is its own k; rec_live = the lane's game
+  // played the tick before (its row then takes the state found at this one)
+  bool rec_wg = false, rec_lane = false, rec_live = false;
+  int64_t rec_j = 0;
+  if constexpr (REC) {
+    rec_wg = w0 && rec_k0 < rc->per_block;
+    rec_lane = mine && rec_k0 + (lane >> 1) < rc->per_block;
+    rec_j = (int64_t)rec_b * rc->per_block + rec_k0 + (lane >> 1);
+  }
   for (int t = 0; t < mt.n_ticks; ++t) {
     // both nets' addresses opaque per tick (k_act_episode32's reason, twice over)
     const float *af1 = aflat1, *af2 = aflat2;
@@ -628,16 +682,48 @@ __device__ __forceinline__ void match_ticks32(const float* aflat1, const char* a
       if (alive && L.p == 0) mt.lengths[L.i] = t + 1;
       const uint64_t any = __ballot(alive);
       if (lane == 0) *sAlive = any != 0;
+      if constexpr (REC) {
+        // slab slab0 + t: the pre-tick state of a game that plays tick t, or
+        // the final state of one that played tick t - 1 and is found ended
+        if (rec_wg) {
+          if (rec_lane && (alive || rec_live))
+            rec_state(*rc, (int64_t)(rc->slab0 + t) * rc->rows + rec_j, L.p, L.pp, L.rot, L.qq, L.qrot, L.ca, L.mi);
+          rec_live = alive;
+        }
+      }
     }
     __syncthreads();
     if (!*sAlive) break;  // workgroup-uniform: every game of the workgroup has ended
     if (w0) {
-      sk::split_finish(at, c, L, sAct[(lane & 1) * 32 + (lane >> 1)], slot);
-      if (L.in && ret) acc += *ret;  // the reward split_finish just stored for this (player, game)
+      const float2 act = sAct[(lane & 1) * 32 + (lane >> 1)];
+      sk::split_finish(at, c, L, act, slot);
+      float r = 0.f;
+      if (L.in && ret) acc += r = *ret;  // the reward split_finish just stored for this (player, game)
+      if constexpr (REC) {
+        if (rec_wg && rec_lane && L.in) {
+          const int64_t at_a = ((int64_t)(rc->slab0 + t) * 2 + L.p) * rc->rows + rec_j;
+          rc->actions[2 * at_a] = act.x;
+          rc->actions[2 * at_a + 1] = act.y;
+          if (rc->rewards && ret) rc->rewards[at_a] = r;
+        }
+      }
     }
     __syncthreads();  // this tick's observations are the next tick's acting rows (this workgroup's own stores)
   }
   if (ret) *ret = acc;
+  if constexpr (REC) {
+    // a game still playing when n_ticks ran out (a break leaves rec_live
+    // false in every lane): its state after the last tick, slab slab0 +
+    // n_ticks, is the lane's own plane stores read back
+    if (rec_wg && rec_lane && rec_live) {
+      const int p = lane & 1;
+      const int64_t h = gt;
+      rec_state(*rc, (int64_t)(rc->slab0 + mt.n_ticks) * rc->rows + rec_j, p, reinterpret_cast<const int2*>(a.v.pos)[h],
+                reinterpret_cast<const double*>(a.v.rot)[h], reinterpret_cast<const int2*>(a.v.qpos)[h],
+                reinterpret_cast<const double*>(a.v.qrot)[h], reinterpret_cast<const int2*>(a.v.qcdage)[h],
+                a.v.misc[gi]);
+    }
+  }
 }
 __global__ void __launch_bounds__(kFwdThreads, kEpisodeWaves) k_act_match32(const float* __restrict__ aflat1,
                                                                             const char* __restrict__ apack1,
@@ -645,7 +731,18 @@ __global__ void __launch_bounds__(kFwdThreads, kEpisodeWaves) k_act_match32(cons
                                                                             const char* __restrict__ apack2,
                                                                             sk::StepArgs a, sk::Cfg c, MatchArgs mt) {
   extern __shared__ __attribute__((aligned(16))) float smem_sl[];
-  match_ticks32(aflat1, apack1, aflat2, apack2, a, c, mt, (char*)smem_sl);
+  match_ticks32<false>(aflat1, apack1, aflat2, apack2, a, c, mt, (char*)smem_sl);
+}
+// k_act_match32 keeping a record: the match is one block of N games, so
+// workgroup b's games are k = 32b .. 32b + 31 of block 0
+__global__ void __launch_bounds__(kFwdThreads, kEpisodeWaves) k_act_match32_rec(const float* __restrict__ aflat1,
+                                                                                const char* __restrict__ apack1,
+                                                                                const float* __restrict__ aflat2,
+                                                                                const char* __restrict__ apack2,
+                                                                                sk::StepArgs a, sk::Cfg c, MatchArgs mt,
+                                                                                RecArgs rc) {
+  extern __shared__ __attribute__((aligned(16))) float smem_sl[];
+  match_ticks32<true>(aflat1, apack1, aflat2, apack2, a, c, mt, (char*)smem_sl, &rc, 0, (int)blockIdx.x * 32);
 }
 
 // League evaluation (sk_env_act_league): every ordered pairing of K actors
@@ -688,7 +785,35 @@ __global__ void __launch_bounds__(kFwdThreads, kEpisodeWaves) k_act_league32(Lea
     if (blockIdx.x == 0 && threadIdx.x == 0 && mt.last_half) *mt.last_half = mt.n_ticks & 1;
     return;
   }
-  match_ticks32((const float*)f1, (const char*)k1, (const float*)f2, (const char*)k2, a, c, mt, (char*)smem_sl);
+  match_ticks32<false>((const float*)f1, (const char*)k1, (const float*)f2, (const char*)k2, a, c, mt,
+                       (char*)smem_sl);
+}
+// k_act_league32 keeping a record: its prologue and guard line for line (a
+// shared wrapper compiled the plain kernel's guard to other code, so each
+// keeps its own); pairing p is block p of the record and the workgroup's
+// first game is game 32 (blockIdx.x - p wgs_per_block) of it, both scalar.  A
+// pairing the guard refuses records nothing.
+__global__ void __launch_bounds__(kFwdThreads, kEpisodeWaves) k_act_league32_rec(LeagueArgs lg, sk::StepArgs a,
+                                                                                    sk::Cfg c, MatchArgs mt,
+                                                                                    RecArgs rc) {
+  extern __shared__ __attribute__((aligned(16))) float smem_sl[];
+  const int p = (int)blockIdx.x / lg.wgs_per_pair;
+  const int i1 = lg.pairs[2 * p], i2 = lg.pairs[2 * p + 1];
+  uint64_t f1 = 0, k1 = 0, f2 = 0, k2 = 0;
+  if ((unsigned)i1 < (unsigned)lg.n_actors && (unsigned)i2 < (unsigned)lg.n_actors) {
+    f1 = lg.nets[2 * i1];
+    k1 = lg.nets[2 * i1 + 1];
+    f2 = lg.nets[2 * i2];
+    k2 = lg.nets[2 * i2 + 1];
+  }
+  if (!f1 || !k1 || !f2 || !k2 || ((f1 | f2) & 3) || ((k1 | k2) & 15)) {
+    const int64_t g = (int64_t)blockIdx.x * 32 + threadIdx.x;
+    if (threadIdx.x < 32 && g < a.n) mt.lengths[g] = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && mt.last_half) *mt.last_half = mt.n_ticks & 1;
+    return;
+  }
+  match_ticks32<true>((const float*)f1, (const char*)k1, (const float*)f2, (const char*)k2, a, c, mt, (char*)smem_sl,
+                      &rc, p, ((int)blockIdx.x - p * rc.wgs_per_block) * 32);
 }
 
 // The opponent-pool training tick (sk_env_act_step_pool): k_act_step32's tick
@@ -1040,6 +1165,50 @@ int sk_launch_act_league32(const uint64_t* nets, int n_actors, const int32_t* pa
   const MatchArgs mt{obs2, returns, lengths, last_half, n_ticks};
   const LeagueArgs lg{nets, pairs, n_actors, block / 32};
   k_act_league32<<<G, kFwdThreads, kActMatchLds, st>>>(lg, a, c, mt);
+  if (hipGetLastError() != hipSuccess) return SK_EHIP;
+  k_episode_finish<<<1, 256, 0, st>>>(lengths, a.n, a.step, nullptr);
+  return hipGetLastError() == hipSuccess ? SK_OK : SK_EHIP;
+}
+
+// the recording twins (sk_env_act_match_rec / sk_env_act_league_rec, csrc/sk_engine.hip, which has checked the
+// record against the launch: rows, slabs, per_block, slab0 + n_ticks and every pointer)
+static RecArgs rec_args(const sk_match_record& r, int wgs_per_block) {
+  return RecArgs{(int2*)r.states.pos,    (double*)r.states.rot,  (int2*)r.states.qpos, (double*)r.states.qrot,
+                 (int2*)r.states.qcdage, (int2*)r.states.misc,   r.actions,            r.rewards,
+                 (int64_t)r.rows,        r.per_block,            r.slab0,              wgs_per_block};
+}
+int sk_launch_act_match32_rec(const float* aflat1, const void* apack1, const float* aflat2, const void* apack2,
+                              const sk::StepArgs& a, const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths,
+                              int32_t* last_half, int n_ticks, const sk_match_record& rec, hipStream_t st) {
+  static bool attr = false;
+  if (!attr) {
+    set_lds32(k_act_match32_rec, kActMatchLds);
+    attr = true;
+  }
+  if (!apack1 || !apack2 || ((((uintptr_t)apack1) | ((uintptr_t)apack2)) & 15)) return SK_EINVAL;
+  if (rec.per_block < 1 || rec.per_block > a.n || rec.rows != rec.per_block) return SK_EINVAL;
+  const unsigned G = (unsigned)((a.n + 31) / 32);
+  const MatchArgs mt{obs2, returns, lengths, last_half, n_ticks};
+  k_act_match32_rec<<<G, kFwdThreads, kActMatchLds, st>>>(aflat1, (const char*)apack1, aflat2, (const char*)apack2, a,
+                                                          c, mt, rec_args(rec, 0));
+  if (hipGetLastError() != hipSuccess) return SK_EHIP;
+  k_episode_finish<<<1, 256, 0, st>>>(lengths, a.n, a.step, nullptr);
+  return hipGetLastError() == hipSuccess ? SK_OK : SK_EHIP;
+}
+int sk_launch_act_league32_rec(const uint64_t* nets, int n_actors, const int32_t* pairs, int block,
+                               const sk::StepArgs& a, const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths,
+                               int32_t* last_half, int n_ticks, const sk_match_record& rec, hipStream_t st) {
+  static bool attr = false;
+  if (!attr) {
+    set_lds32(k_act_league32_rec, kActMatchLds);
+    attr = true;
+  }
+  if (!nets || !pairs || n_actors < 1 || block <= 0 || block % 32 || a.n % block) return SK_EINVAL;
+  if (rec.per_block < 1 || rec.per_block > block || rec.rows != (a.n / block) * rec.per_block) return SK_EINVAL;
+  const unsigned G = (unsigned)(a.n / 32);
+  const MatchArgs mt{obs2, returns, lengths, last_half, n_ticks};
+  const LeagueArgs lg{nets, pairs, n_actors, block / 32};
+  k_act_league32_rec<<<G, kFwdThreads, kActMatchLds, st>>>(lg, a, c, mt, rec_args(rec, block / 32));
   if (hipGetLastError() != hipSuccess) return SK_EHIP;
   k_episode_finish<<<1, 256, 0, st>>>(lengths, a.n, a.step, nullptr);
   return hipGetLastError() == hipSuccess ? SK_OK : SK_EHIP;

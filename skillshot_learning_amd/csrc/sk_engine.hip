@@ -1227,6 +1227,84 @@ int sk_env_act_league(sk_env* e, const uint64_t* nets, int32_t n_actors, const i
   return SK_OK;
 }
 
+// a match record against its launch of `blocks` blocks of `block` games (include/skillshot.h)
+static int rec_check(const sk_match_record* rec, int64_t blocks, int64_t block, int32_t n_ticks,
+                     const float* returns) {
+  if (!rec) return fail(SK_EINVAL, "rec is NULL");
+  const sk_state_view& v = rec->states;
+  if (!v.pos || !v.rot || !v.qpos || !v.qrot || !v.qcdage || !v.misc || !rec->actions)
+    return fail(SK_EINVAL, "a plane of rec->states or rec->actions is NULL");
+  if (rec->per_block < 1 || rec->per_block > block)
+    return fail(SK_EINVAL, "rec->per_block must lie in [1, the block's games]");
+  if ((int64_t)rec->rows != blocks * rec->per_block) return fail(SK_EINVAL, "rec->rows must be blocks * per_block");
+  if (rec->slabs < 1 || (int64_t)v.n_envs != (int64_t)rec->slabs * rec->rows)
+    return fail(SK_EINVAL, "rec->states.n_envs must be slabs * rows");
+  if (rec->slab0 < 0) return fail(SK_EINVAL, "rec->slab0 must not be negative");
+  if ((int64_t)rec->slab0 + n_ticks + 1 > rec->slabs)
+    return fail(SK_EINVAL, "rec->slab0 + n_ticks + 1 slabs do not fit rec->slabs");
+  if (rec->rewards && !returns) return fail(SK_EINVAL, "rec->rewards needs returns (no reward is computed without it)");
+  if ((((uintptr_t)v.pos) | ((uintptr_t)v.rot) | ((uintptr_t)v.qpos) | ((uintptr_t)v.qrot) | ((uintptr_t)v.qcdage) |
+       ((uintptr_t)v.misc)) & 7)
+    return fail(SK_EINVAL, "the planes of rec->states must be 8-byte aligned");
+  if ((((uintptr_t)rec->actions) | ((uintptr_t)rec->rewards)) & 3)
+    return fail(SK_EINVAL, "rec->actions / rec->rewards must be 4-byte aligned");
+  return SK_OK;
+}
+
+int sk_env_act_match_rec(sk_env* e, const float* actor1_flat, const void* actor1_pack, const float* actor2_flat,
+                         const void* actor2_pack, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
+                         int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, const sk_match_record* rec,
+                         void* stream) {
+  SK_CHECK_ENV(e);
+  if (!actor1_flat || !actor2_flat || !actor1_pack || !actor2_pack || !obs2 || !lengths || n_ticks <= 0)
+    return fail(SK_EINVAL, "an actor's flat / pack, obs2 or lengths is NULL, or n_ticks <= 0");
+  if ((((uintptr_t)actor1_pack) | ((uintptr_t)actor2_pack)) & 15)
+    return fail(SK_EINVAL, "actor1_pack / actor2_pack must be 16-byte aligned");
+  if ((((uintptr_t)lengths) | ((uintptr_t)returns) | ((uintptr_t)last_half)) & 3)
+    return fail(SK_EINVAL, "lengths / returns / last_half must be 4-byte aligned");
+  int rc = rec_check(rec, 1, e->n, n_ticks, returns);
+  if (rc != SK_OK) return rc;
+  StepArgs a;  // (as sk_env_act_match)
+  rc = act_step_args(e, obs2, nullptr, obs2, returns, reward_kind, nullptr, nullptr, tick_limit, 0, 0, nullptr,
+                     nullptr, 0, nullptr, nullptr, nullptr, a);
+  if (rc != SK_OK) return rc;
+  if (e->host) return fail(SK_EINVAL, "sk_env_act_match_rec runs on the GPU backend");
+  rc = sk_launch_act_match32_rec(actor1_flat, actor1_pack, actor2_flat, actor2_pack, a, e->dcfg, obs2, returns,
+                                 lengths, last_half, n_ticks, *rec, (hipStream_t)stream);
+  if (rc != SK_OK) return fail(rc, "k_act_match32_rec launch failed");
+  e->parity ^= 1;
+  return SK_OK;
+}
+
+int sk_env_act_league_rec(sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
+                          int32_t block, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
+                          int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, const sk_match_record* rec,
+                          void* stream) {
+  SK_CHECK_ENV(e);
+  if (!nets || !pairs) return fail(SK_EINVAL, "the nets or the pairs table is NULL");
+  if (!obs2 || !lengths || n_ticks <= 0) return fail(SK_EINVAL, "obs2 or lengths is NULL, or n_ticks <= 0");
+  if (n_actors < 1 || n_pairs < 1) return fail(SK_EINVAL, "n_actors and n_pairs must be at least 1");
+  if (block <= 0 || block % 32) return fail(SK_EINVAL, "block must be a positive multiple of 32");
+  if ((int64_t)e->n != (int64_t)n_pairs * block) return fail(SK_EINVAL, "the env must hold n_pairs * block games");
+  if ((((uintptr_t)nets) & 7) || (((uintptr_t)pairs) & 3))
+    return fail(SK_EINVAL, "nets must be 8-byte aligned, pairs 4-byte");
+  if ((((uintptr_t)lengths) | ((uintptr_t)returns) | ((uintptr_t)last_half)) & 3)
+    return fail(SK_EINVAL, "lengths / returns / last_half must be 4-byte aligned");
+  if (((uintptr_t)obs2) & 15) return fail(SK_EINVAL, "obs2 must be 16-byte aligned");
+  int rc = rec_check(rec, n_pairs, block, n_ticks, returns);
+  if (rc != SK_OK) return rc;
+  if (e->host) return fail(SK_EINVAL, "sk_env_act_league_rec runs on the GPU backend");
+  StepArgs a;  // (as sk_env_act_match)
+  rc = act_step_args(e, obs2, nullptr, obs2, returns, reward_kind, nullptr, nullptr, tick_limit, 0, 0, nullptr,
+                     nullptr, 0, nullptr, nullptr, nullptr, a);
+  if (rc != SK_OK) return rc;
+  rc = sk_launch_act_league32_rec(nets, n_actors, pairs, block, a, e->dcfg, obs2, returns, lengths, last_half, n_ticks,
+                                  *rec, (hipStream_t)stream);
+  if (rc != SK_OK) return fail(rc, "k_act_league32_rec launch failed");
+  e->parity ^= 1;
+  return SK_OK;
+}
+
 int sk_env_act_step_pool(sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
                          int32_t block, int32_t noisy_actor, const float* acting_obs, float* actions, float noise_sd,
                          float action_sd, uint64_t noise_seed, uint64_t* call_counter, float* obs, float* reward,

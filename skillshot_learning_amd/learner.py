@@ -1153,7 +1153,8 @@ class SkillshotLearner:
         return int(max(1, min(self.game_environment.tick_limit, (share * free) // per_tick)))
 
     # ------------------------------------------------------------ evaluation
-    def evaluate(self, opponent=None, games=None, swap_sides=True, tick_limit=None, reward="looking", seed=None):
+    def evaluate(self, opponent=None, games=None, swap_sides=True, tick_limit=None, reward="looking", seed=None,
+                 record=0):
         """Head-to-head evaluation: this learner's actor against `opponent`,
         both deterministic (no exploration noise), over `games` whole games.
 
@@ -1169,6 +1170,11 @@ class SkillshotLearner:
                   hit-tested first (check_collision, SkillshotGame.py:58-94),
                   and the swap cancels that seat bias
         seed      of the evaluation env (default: derived from the learner's)
+        record    keep what the first `record` games of each leg did at every
+                  tick: the result gains `records`, one MatchRecord per leg
+                  (record.py: states, actions, rewards, boards); both legs'
+                  slab 0 are the same start states.  The tallies are those of
+                  the same call without it, on either path.
 
         The games run on a dedicated evaluation env (created on first use,
         kept per (games, tick_limit, seed)), rewound at every call: the same
@@ -1190,25 +1196,37 @@ class SkillshotLearner:
         sums of `reward` ("looking" / "simple")."""
         n = int(self.n_envs if games is None else games)
         limit = int(self.model_param_game_tick_limit if tick_limit is None else tick_limit)
+        r = self._record_rows(record, n)
         g = self._eval_env(n, limit, seed)
         mine, theirs = self._match_actors(opponent)
         use_kernel = self._match_kernel_usable() and os.environ.get("SK_MATCH_KERNEL", "1") != "0"
         g.step_counter = 0
         g.reset(random_positions=self.use_random_start)
         start = g.state_dict() if swap_sides else None
-        rows = []
+        rows, records = [], []
         for seat in ((1, 2) if swap_sides else (1,)):
             if seat == 2:
                 g.load_state_dict(start)
             a1, a2 = (mine, theirs) if seat == 1 else (theirs, mine)
-            rows.append(self._match_leg(g, a1, a2, seat, limit, reward, use_kernel))
+            rows.append(self._match_leg(g, a1, a2, seat, limit, reward, use_kernel, record=r, records=records))
         flat = torch.stack(rows).cpu()  # the one host read: six scalars per leg
         legs = [_match_summary(n, *flat[k].tolist(), seat=k + 1) for k in range(len(rows))]
         total = _match_summary(n * len(rows), *flat.sum(0).tolist())
         total["legs"] = legs
+        if r:
+            total["records"] = records
         return total
 
-    def league(self, actors, games=None, tick_limit=None, reward="looking", seed=None):
+    @staticmethod
+    def _record_rows(record, games):
+        """evaluate's / league's `record` argument as a number of games"""
+        if isinstance(record, bool) or not isinstance(record, (int, np.integer)):
+            raise TypeError("record must be a number of games")
+        if not 0 <= int(record) <= games:
+            raise ValueError(f"record must lie in [0, {games}], the games played")
+        return int(record)
+
+    def league(self, actors, games=None, tick_limit=None, reward="looking", seed=None, record=0):
         """Round robin of K actors: every ORDERED pairing (i, j), i != j,
         plays `games` whole games, i in seat 1 and j in seat 2, all from
         evaluate's start states (the same `games`, tick_limit and seed give
@@ -1220,6 +1238,11 @@ class SkillshotLearner:
                 built for them are held until the next league call (a holder
                 of league's own, not evaluate's 8-entry cache).
         games   games per ordered pairing (default n_envs)
+        record  keep what the first `record` games of every pairing did at
+                every tick: the result gains `record`, one MatchRecord with
+                `record` rows per pairing in the pairings' order, whose
+                `pairs` names each row's (i, j) and whose `games` its game
+                among evaluate's start states
 
         With the fp32 acting kernel on a GPU all K (K - 1) pairings play in
         ONE launch (VecSkillshotGame.act_league) on a league env of K (K - 1)
@@ -1253,24 +1276,31 @@ class SkillshotLearner:
                    for e in entries]
         self._league_actors = used  # this call's nets stay, earlier leagues' go
         pairs = [(i, j) for i in range(K) for j in range(K) if i != j]
+        r = self._record_rows(record, n)
+        rec = None
         g = self._eval_env(n, limit, seed)
         g.step_counter = 0
         g.reset(random_positions=self.use_random_start)
         use_kernel = (self._match_kernel_usable() and all(p[1] is not None for p in players) and
                       os.environ.get("SK_LEAGUE_KERNEL", "1") != "0")
         if use_kernel:
-            rows = self._league_launch(g, [p[1] for p in players], pairs, n, limit, reward)
+            rows = self._league_launch(g, [p[1] for p in players], pairs, n, limit, reward, record=r)
+            if r:
+                rows, rec = rows
         else:
             start = g.state_dict()
-            legs = []
+            legs, recs = [], []
             for k, (i, j) in enumerate(pairs):
                 if k:
                     g.load_state_dict(start)
                 legs.append(self._match_leg(g, players[i], players[j], 1, limit, reward,
                                             self._match_kernel_usable() and players[i][1] is not None and
                                             players[j][1] is not None and
-                                            os.environ.get("SK_MATCH_KERNEL", "1") != "0"))
+                                            os.environ.get("SK_MATCH_KERNEL", "1") != "0", record=r, records=recs))
             rows = torch.stack(legs)
+            if r:
+                from .record import MatchRecord
+                rec = MatchRecord.concat(recs, pairs)
         flat = rows.cpu().numpy()  # the one host read: six scalars per pairing
         tab = np.zeros((6, K, K))
         for k, (i, j) in enumerate(pairs):
@@ -1284,18 +1314,23 @@ class SkillshotLearner:
         def ints(a):
             return [[int(v) for v in r] for r in a]
 
-        return dict(n_actors=K, games=n, seat_wins=ints(sw), seat_losses=ints(sl), seat_draws=ints(sd),
-                    mean_ticks=(tab[3] / n).tolist(), mean_return=(tab[4] / n).tolist(),
-                    opponent_mean_return=(tab[5] / n).tolist(), wins=ints(wins), draws=ints(draws),
-                    score=score.tolist(), elo=elo.tolist(),
-                    ranking=sorted(range(K), key=lambda i: (-elo[i], i)))
+        res = dict(n_actors=K, games=n, seat_wins=ints(sw), seat_losses=ints(sl), seat_draws=ints(sd),
+                   mean_ticks=(tab[3] / n).tolist(), mean_return=(tab[4] / n).tolist(),
+                   opponent_mean_return=(tab[5] / n).tolist(), wins=ints(wins), draws=ints(draws),
+                   score=score.tolist(), elo=elo.tolist(),
+                   ranking=sorted(range(K), key=lambda i: (-elo[i], i)))
+        if r:
+            res["record"] = rec
+        return res
 
-    def _league_launch(self, g, kernels, pairs, games, limit, reward):
+    def _league_launch(self, g, kernels, pairs, games, limit, reward, record=0):
         """league's pairings in one launch from env g's current (start) state:
         fp64 [P, 6] on the device, _match_leg's tallies for seat 1 of every
         pairing.  The reward sums are taken as _match_leg takes them, an fp32
         sum over a [2, games] buffer per pairing, so both paths of league
-        return the same numbers."""
+        return the same numbers.  record > 0: (the tallies, the launch's
+        MatchRecord of `record` rows per pairing, its `games` counted within
+        the pairing as the pair-by-pair path counts them)."""
         from .vec_env import PLANES, VecSkillshotGame
         P, block = len(pairs), 32 * ((games + 31) // 32)
         envs = self.__dict__.setdefault("_league_envs", {})
@@ -1316,7 +1351,8 @@ class SkillshotLearner:
         obs, _ = g.observe(reward=reward)
         lg._league_obs[:, :, :games] = obs[:, None]
         m = lg.act_league(kernels, pairs, block, lg._league_obs, n_ticks=limit, reward=reward,
-                          out=getattr(lg, "_league_bufs", None))
+                          out=getattr(lg, "_league_bufs", None), record=record)
+        rec = m.pop("record", None)
         lg._league_bufs = m
         w = lg.winner_id.view(P, block)[:, :games]
         ticks = lg.ticks.view(P, block)[:, :games]
@@ -1327,8 +1363,12 @@ class SkillshotLearner:
             sums.append(buf[0].sum())
             sums.append(buf[1].sum())
         sums = torch.stack(sums).view(P, 2).double()
-        return torch.stack([(w == 2).sum(1).double(), (w == 1).sum(1).double(), (w == 0).sum(1).double(),
-                            ticks.sum(1).double(), sums[:, 0], sums[:, 1]], 1)
+        tallies = torch.stack([(w == 2).sum(1).double(), (w == 1).sum(1).double(), (w == 0).sum(1).double(),
+                               ticks.sum(1).double(), sums[:, 0], sums[:, 1]], 1)
+        if rec is None:
+            return tallies
+        rec.games = rec.games % block
+        return tallies, rec
 
     def _eval_env(self, games, tick_limit, seed):
         from .vec_env import VecSkillshotGame
@@ -1347,20 +1387,28 @@ class SkillshotLearner:
         return (self.precision == "fp32" and self.device.type == "cuda" and
                 getattr(self.actor_kernel, "fused_act_step", False))
 
-    def _match_leg(self, g, a1, a2, seat, limit, reward, use_kernel):
+    def _match_leg(self, g, a1, a2, seat, limit, reward, use_kernel, record=0, records=None):
         """one leg on env g from its current state, seat 1 acting from a1 and
         seat 2 from a2 (each a pair of _match_actors): six 0-d fp64 tallies on
         the device, from the point of view of the player in `seat` — wins,
         losses, draws, the games' ticks, the own and the other seat's reward
-        sums (fp32 sums over the games)"""
+        sums (fp32 sums over the games).  record > 0: the MatchRecord of the
+        leg's first `record` games is appended to `records`."""
         obs, _ = g.observe(reward=reward)
         if use_kernel:
             m = g.act_match(a1[1], a2[1], obs, n_ticks=limit, reward=reward,
-                            out=getattr(g, "_match_bufs", None))
+                            out=getattr(g, "_match_bufs", None), record=record)
+            rec = m.pop("record", None)
             g._match_bufs = m
             ret, winner, ticks = m["returns"], g.winner_id, g.ticks
         else:
-            ret, winner, ticks = self._match_loop(g, a1[0], a2[0], obs, reward)
+            rec = None
+            if record:
+                from .record import MatchRecord
+                rec = MatchRecord.allocate(g.tick_limit + 1, torch.arange(record), g.config, g.device)
+            ret, winner, ticks = self._match_loop(g, a1[0], a2[0], obs, reward, record=rec)
+        if rec is not None:
+            records.append(rec)
         o = match_outcomes(winner, seat)
         return torch.stack([v.double() for v in (o["wins"], o["losses"], o["draws"], ticks.sum(),
                                                  ret[seat - 1].sum(), ret[2 - seat].sum())])
@@ -1424,25 +1472,40 @@ class SkillshotLearner:
         return pair(net, ent["kernel"])
 
     @torch.no_grad()
-    def _match_loop(self, g, act1, act2, obs, reward):
+    def _match_loop(self, g, act1, act2, obs, reward, record=None):
         """one leg tick by tick on env g: seat 1 acts with act1, seat 2 with
         act2; returns (fp32 reward sums [2, N] over each game's own ticks, the
         games' final winner_id and ticks).  step(auto_reset=False) keeps
         moving the players of ended games, so an ended game's outcome is kept
-        from the tick it ended on (model_train's masking, :302-318)."""
+        from the tick it ended on (model_train's masking, :302-318).  record
+        (a MatchRecord over games of g): filled as the one-launch kernels fill
+        theirs, for the same reason — a row takes its game's pre-tick state,
+        actions and rewards only while the game lives, and the post-tick
+        state at the tick it ends."""
         n, dev = g.n, g.device
         alive = g.game_live & (g.ticks < g.tick_limit)
         acc = torch.zeros((2, n), dtype=torch.float32, device=dev)
         ticks, winner = g.ticks.clone(), g.winner_id.clone()
+        played = torch.zeros(n, dtype=torch.int32, device=dev)
+        t = 0
         while bool(alive.any()):
             act = torch.stack((act1(obs[0]), act2(obs[1])))
+            if record is not None:
+                ar = record.loop_before(g, t, alive)
             out = g.step(act, obs=True, reward=reward, auto_reset=False)
+            if record is not None:
+                record.loop_after(g, t, ar, act, out["reward"], out["done"])
+                played += alive.int()
             acc = torch.where(alive[None, :], acc + out["reward"], acc)
             newly = alive & out["done"].bool()
             ticks = torch.where(newly, g.ticks, ticks)
             winner = torch.where(newly, out["winner"], winner)
             alive = alive & ~out["done"].bool()
             obs = out["obs"]
+            t += 1
+        if record is not None:
+            record.lengths.copy_(played[record.games])
+            record.ticks_run = t
         return acc, winner, ticks
 
     # ------------------------------------------------------------ on-disk formats (persist.py)

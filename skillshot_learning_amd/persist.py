@@ -138,3 +138,38 @@ def load_training_boards(save_location):
     """load_training_boards (:194-204): the list of per-epoch [ticks, 250, 250] boards."""
     d = np.load(os.path.join(save_location, BOARDS_DIR, "training_boards.npz"))
     return [d[f"epoch_{k}"] for k in range(len(d.files))]
+
+
+def save_match_record(path, record):
+    """A MatchRecord (record.py) as one .npz of arrays and settings: the six
+    state planes, actions, rewards, lengths, games, the rows' pairings (a
+    league's; an empty array otherwise), per_block, ticks_run and the
+    sk_config's fields.  Returns the path written (numpy appends .npz to a
+    name without it)."""
+    from .record import config_arrays
+    r = record.cpu()
+    d = {f"states_{name}": t.numpy() for name, t in r.states.items()}
+    d.update(actions=r.actions.numpy(), rewards=r.rewards.numpy(), lengths=r.lengths.numpy(), games=r.games.numpy(),
+             pairs=np.asarray(r.pairs if r.pairs is not None else [], dtype=np.int64).reshape(-1, 2),
+             has_pairs=np.asarray(r.pairs is not None), per_block=np.asarray(r.per_block),
+             ticks_run=np.asarray(r.ticks_run))
+    d.update(config_arrays(r.config))
+    path = str(path)
+    if not path.endswith(".npz"):
+        path += ".npz"
+    loc = os.path.dirname(path)
+    if loc:
+        os.makedirs(loc, exist_ok=True)
+    np.savez_compressed(path, **d)
+    return path
+
+
+def load_match_record(path):
+    """save_match_record's file as a MatchRecord on the host (no GPU needed)."""
+    from .record import _PLANES, MatchRecord, config_from_arrays
+    d = np.load(str(path))
+    states = {name: torch.from_numpy(d[f"states_{name}"]) for name, _, _ in _PLANES}
+    pairs = [tuple(int(v) for v in row) for row in d["pairs"]] if bool(d["has_pairs"]) else None
+    return MatchRecord(states, torch.from_numpy(d["actions"]), torch.from_numpy(d["rewards"]),
+                       torch.from_numpy(d["lengths"]), torch.from_numpy(d["games"]), config_from_arrays(d),
+                       pairs=pairs, per_block=int(d["per_block"]), ticks_run=int(d["ticks_run"]))

@@ -510,7 +510,33 @@ class VecSkillshotGame:
             prs.copy_(torch.tensor(plist, dtype=torch.int32))
         return nets, prs, (addr, plist)
 
-    def act_match(self, actor1, actor2, start_obs, n_ticks=None, reward="looking", out=None, resume=False):
+    def _match_record(self, record, blocks, block, resume):
+        """the MatchRecord of a recording act_match / act_league call (None
+        for record None / 0): an int allocates one of that many rows per block
+        of `block` games and tick_limit + 1 slabs, a MatchRecord is checked
+        against the call and reused; without resume it starts at slab 0"""
+        if record is None or (isinstance(record, int) and not isinstance(record, bool) and record == 0):
+            return None
+        from .record import MatchRecord
+        if isinstance(record, MatchRecord):
+            rec = record
+        else:
+            if isinstance(record, bool) or not isinstance(record, (int, np.integer)):
+                raise TypeError("record must be None, a number of games per block or a MatchRecord")
+            per = int(record)
+            if not 1 <= per <= block:
+                raise ValueError(f"record must lie in [1, {block}], the games of a block")
+            games = (torch.arange(blocks)[:, None] * block + torch.arange(per)[None, :]).reshape(-1)
+            rec = MatchRecord.allocate(self.tick_limit + 1, games, self.config, self.device, per_block=per)
+        if not 1 <= rec.per_block <= block:
+            raise ValueError(f"the record keeps {rec.per_block} games per block, a block has {block}")
+        rec.check_layout(blocks * rec.per_block, self.device)
+        if not resume:
+            rec.ticks_run = 0
+        return rec
+
+    def act_match(self, actor1, actor2, start_obs, n_ticks=None, reward="looking", out=None, resume=False,
+                  record=None):
         """Two actors play every game head to head in ONE launch
         (sk_env_act_match; the loop of SkillshotLearner.py:302-318 with two
         policies): seat 1 (player id 1) acts from actor1, seat 2 from actor2
@@ -527,7 +553,16 @@ class VecSkillshotGame:
         lengths and returns then carry on from `prev` (the sums equal one
         long launch's, bit for bit).  out without resume only reuses the
         buffers.  The device step counter advances by max(lengths of this
-        call); neither actor's noise call number moves.  Any N >= 1."""
+        call); neither actor's noise call number moves.  Any N >= 1.
+
+        record: keep what the first games did at every tick (record.py,
+        sk_env_act_match_rec: the same launch, a few more stores per tick).
+        An int r records games 0 .. r - 1 into a new MatchRecord of
+        tick_limit + 1 slabs, returned as out["record"]; a MatchRecord is
+        reused.  With resume=True the record continues at the slab the earlier
+        calls' ticks reached (record.ticks_run), and its lengths follow
+        out["lengths"].  A recording call runs no more ticks than the record
+        has slabs left for; once they are used up the call runs unrecorded."""
         if self.is_cpu:
             raise SkillshotError("act_match runs on the GPU backend (SkillshotLearner.evaluate loops on the CPU one)")
         T = int(self.tick_limit if n_ticks is None else n_ticks)
@@ -553,18 +588,33 @@ class VecSkillshotGame:
         if not resume:
             ret.zero_()
         p1, p2 = actor1.ensure_pack(), actor2.ensure_pack()
-        check(self._L.sk_env_act_match(self._h, _ptr(actor1.flat), _ptr(p1), _ptr(actor2.flat), _ptr(p2), _ptr(obs2),
-                                       _ptr(ret), _ptr(call_ln), _ptr(o.get("last_half")), T,
-                                       REWARD_KINDS[reward], self.tick_limit, self._stream()))
+        rec = self._match_record(record, 1, self.n, resume)
+        T_rec = min(T, rec.slabs - 1 - rec.ticks_run) if rec is not None else 0
+        if T_rec >= 1:
+            st = rec.c_struct(rec.ticks_run)
+            check(self._L.sk_env_act_match_rec(self._h, _ptr(actor1.flat), _ptr(p1), _ptr(actor2.flat), _ptr(p2),
+                                               _ptr(obs2), _ptr(ret), _ptr(call_ln), _ptr(o.get("last_half")), T_rec,
+                                               REWARD_KINDS[reward], self.tick_limit, ctypes.byref(st),
+                                               self._stream()))
+            rec.ticks_run += T_rec
+        else:
+            check(self._L.sk_env_act_match(self._h, _ptr(actor1.flat), _ptr(p1), _ptr(actor2.flat), _ptr(p2),
+                                           _ptr(obs2), _ptr(ret), _ptr(call_ln), _ptr(o.get("last_half")), T,
+                                           REWARD_KINDS[reward], self.tick_limit, self._stream()))
         torch.where((call_ln & 1).bool()[None, :, None], obs2[1], obs2[0], out=obs)
         if resume:
             total += call_ln
         else:
             total.copy_(call_ln)
-        return dict(lengths=total, returns=ret, obs=obs, obs2=obs2, call_lengths=call_ln,
-                    last_half=o.get("last_half"))
+        res = dict(lengths=total, returns=ret, obs=obs, obs2=obs2, call_lengths=call_ln,
+                   last_half=o.get("last_half"))
+        if rec is not None:
+            torch.index_select(total, 0, rec.games, out=rec.lengths)
+            res["record"] = rec
+        return res
 
-    def act_league(self, actors, pairs, block, start_obs, n_ticks=None, reward="looking", out=None, resume=False):
+    def act_league(self, actors, pairs, block, start_obs, n_ticks=None, reward="looking", out=None, resume=False,
+                   record=None):
         """Every pairing of a league in ONE launch (sk_env_act_league):
         the env holds len(pairs) blocks of `block` games (a multiple of 32),
         and the games of block p play act_match's match with seat 1 acting
@@ -577,7 +627,10 @@ class VecSkillshotGame:
         pairs) are kept in the returned dict (`nets`, `pairs`) and uploaded
         again only when the actors' buffers or `pairs` differ from the call
         that made them, so a repeated or captured call with out= allocates
-        and uploads nothing."""
+        and uploads nothing.  record: act_match's, per pairing — an int r
+        records the first r games of every block (row p r + k = game k of
+        pairing p; the record's `pairs` names each row's pairing); a pairing
+        the kernel's guard refuses and the pad games record nothing."""
         if self.is_cpu:
             raise SkillshotError("act_league runs on the GPU backend (SkillshotLearner.league loops on the CPU one)")
         o = out or {}
@@ -604,16 +657,31 @@ class VecSkillshotGame:
         obs2[0].copy_(start)
         if not resume:
             ret.zero_()
-        check(self._L.sk_env_act_league(self._h, _ptr(nets), len(actors), _ptr(prs), len(plist), block, _ptr(obs2),
-                                        _ptr(ret), _ptr(call_ln), _ptr(o.get("last_half")), T,
-                                        REWARD_KINDS[reward], self.tick_limit, self._stream()))
+        rec = self._match_record(record, len(plist), block, resume)
+        T_rec = min(T, rec.slabs - 1 - rec.ticks_run) if rec is not None else 0
+        if T_rec >= 1:
+            st = rec.c_struct(rec.ticks_run)
+            check(self._L.sk_env_act_league_rec(self._h, _ptr(nets), len(actors), _ptr(prs), len(plist), block,
+                                                _ptr(obs2), _ptr(ret), _ptr(call_ln), _ptr(o.get("last_half")), T_rec,
+                                                REWARD_KINDS[reward], self.tick_limit, ctypes.byref(st),
+                                                self._stream()))
+            rec.ticks_run += T_rec
+        else:
+            check(self._L.sk_env_act_league(self._h, _ptr(nets), len(actors), _ptr(prs), len(plist), block,
+                                            _ptr(obs2), _ptr(ret), _ptr(call_ln), _ptr(o.get("last_half")), T,
+                                            REWARD_KINDS[reward], self.tick_limit, self._stream()))
         torch.where((call_ln & 1).bool()[None, :, None], obs2[1], obs2[0], out=obs)
         if resume:
             total += call_ln
         else:
             total.copy_(call_ln)
-        return dict(lengths=total, returns=ret, obs=obs, obs2=obs2, call_lengths=call_ln,
-                    last_half=o.get("last_half"), nets=nets, pairs=prs, tables=tables)
+        res = dict(lengths=total, returns=ret, obs=obs, obs2=obs2, call_lengths=call_ln,
+                   last_half=o.get("last_half"), nets=nets, pairs=prs, tables=tables)
+        if rec is not None:
+            torch.index_select(total, 0, rec.games, out=rec.lengths)
+            rec.pairs = [plist[p] for p in range(len(plist)) for _ in range(rec.per_block)]
+            res["record"] = rec
+        return res
 
     def act_step_pool(self, actors, pairs, block, acting_obs, noisy=None, noise_sd=0.0, action_sd=0.0, ring=None,
                       reward="looking", auto_reset=True, reset_obs=True, out=None, actions=None, total_copy=None):
