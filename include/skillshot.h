@@ -302,7 +302,13 @@ int sk_env_act_episode(sk_env* env, const float* actor_flat, const void* actor_p
  * (nothing to do after an even n_ticks; after an odd one copy those games'
  * rows of half 1 to half 0).  Any N >= 1.  The step counter advances by max_i lengths[i], the
  * iterations of the per-tick loop this replaces (sk_env_act_episode's second
- * one-workgroup launch); no episode counters.  Stream-ordered and
+ * one-workgroup launch); no episode counters.
+ * SK_EINVAL with a message, before any launch, for a NULL flat, pack, obs2 or
+ * lengths, n_ticks <= 0, a misaligned pointer, a bad reward_kind, and the CPU
+ * backend.  The refusal order, which sk_env_act_league, the two _rec twins
+ * and sk_env_act_step_pool share: a NULL handle; then every argument; then the
+ * match record, where one is kept; and last, with all of those in order, a
+ * CPU-backend handle, refused as such.  Stream-ordered and
  * graph-capturable.  GPU backend only. */
 int sk_env_act_match(sk_env* env, const float* actor1_flat, const void* actor1_pack, const float* actor2_flat,
                      const void* actor2_pack, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
@@ -326,8 +332,8 @@ int sk_env_act_match(sk_env* env, const float* actor1_flat, const void* actor1_p
  * in a later call: as sk_env_act_match.  SK_EINVAL, before any launch, for a
  * NULL table, obs2 or lengths, n_ticks <= 0, n_actors < 1, n_pairs < 1,
  * block <= 0 or block % 32 != 0, an env that does not hold n_pairs * block
- * games, a misaligned pointer, and the CPU backend.  Stream-ordered and
- * graph-capturable.  GPU backend only. */
+ * games, a misaligned pointer, and the CPU backend, in sk_env_act_match's
+ * order.  Stream-ordered and graph-capturable.  GPU backend only. */
 int sk_env_act_league(sk_env* env, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
                       int32_t block, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
                       int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, void* stream);
@@ -360,7 +366,8 @@ int sk_env_act_league(sk_env* env, const uint64_t* nets, int32_t n_actors, const
  * rows != blocks * per_block, states.n_envs != slabs * rows, slab0 < 0,
  * slab0 + n_ticks + 1 > slabs, rewards without returns, a misaligned pointer
  * (8 bytes for the planes, 4 bytes for actions and rewards), and the CPU
- * backend.  Stream-ordered and graph-capturable.  GPU backend only. */
+ * backend, in sk_env_act_match's order.  Stream-ordered and
+ * graph-capturable.  GPU backend only. */
 typedef struct sk_match_record {
   sk_state_view states;   /* n_envs = slabs * rows; device planes */
   float* actions;         /* [slabs - 1][2][rows][2] */
@@ -405,7 +412,8 @@ int sk_env_act_league_rec(sk_env* env, const uint64_t* nets, int32_t n_actors, c
  * n_actors < 1, n_pairs < 1, block <= 0 or block % 32 != 0, an env that does
  * not hold n_pairs * block games, noisy_actor outside [-1, n_actors), a
  * misaligned pointer, sk_env_act_step's ring and reward_kind checks, and the
- * CPU backend.  Stream-ordered and graph-capturable.  GPU backend only. */
+ * CPU backend, in sk_env_act_match's order.  Stream-ordered and
+ * graph-capturable.  GPU backend only. */
 int sk_env_act_step_pool(sk_env* env, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
                          int32_t block, int32_t noisy_actor, const float* acting_obs, float* actions, float noise_sd,
                          float action_sd, uint64_t noise_seed, uint64_t* call_counter, float* obs, float* reward,

@@ -1131,91 +1131,73 @@ int sk_launch_act_episode32(const float* aflat, const void* apack, float sd, flo
   return hipGetLastError() == hipSuccess ? SK_OK : SK_EHIP;
 }
 
-// two actors' matches in one launch (sk_env_act_match, csrc/sk_engine.hip): any a.n >= 1
-int sk_launch_act_match32(const float* aflat1, const void* apack1, const float* aflat2, const void* apack2,
-                          const sk::StepArgs& a, const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths,
-                          int32_t* last_half, int n_ticks, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    set_lds32(k_act_match32, kActMatchLds);
-    attr = true;
-  }
-  if (!apack1 || !apack2 || ((((uintptr_t)apack1) | ((uintptr_t)apack2)) & 15)) return SK_EINVAL;
-  const unsigned G = (unsigned)((a.n + 31) / 32);
-  const MatchArgs mt{obs2, returns, lengths, last_half, n_ticks};
-  k_act_match32<<<G, kFwdThreads, kActMatchLds, st>>>(aflat1, (const char*)apack1, aflat2, (const char*)apack2, a, c,
-                                                      mt);
-  if (hipGetLastError() != hipSuccess) return SK_EHIP;
-  k_episode_finish<<<1, 256, 0, st>>>(lengths, a.n, a.step, nullptr);
-  return hipGetLastError() == hipSuccess ? SK_OK : SK_EHIP;
+// The match family's launchers.  The entry points (csrc/sk_engine.hip) have checked every argument, a record
+// against its launch included (rows, slabs, per_block, slab0 + n_ticks and every pointer); what a kernel's
+// addressing rests on is checked here again.
+// a seating: nets / pairs are device tables, a.n = n_pairs * block, block % 32 == 0
+static bool seating_ok(const uint64_t* nets, int n_actors, const int32_t* pairs, int block, const sk::StepArgs& a) {
+  return nets && pairs && n_actors >= 1 && block > 0 && block % 32 == 0 && a.n % block == 0;
 }
-
-// every pairing of a league in one launch (sk_env_act_league, csrc/sk_engine.hip): a.n = n_pairs * block,
-// block % 32 == 0; nets / pairs are device tables
-int sk_launch_act_league32(const uint64_t* nets, int n_actors, const int32_t* pairs, int block, const sk::StepArgs& a,
-                           const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
-                           int n_ticks, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    set_lds32(k_act_league32, kActMatchLds);
-    attr = true;
-  }
-  if (!nets || !pairs || n_actors < 1 || block <= 0 || block % 32 || a.n % block) return SK_EINVAL;
-  const unsigned G = (unsigned)(a.n / 32);
-  const MatchArgs mt{obs2, returns, lengths, last_half, n_ticks};
-  const LeagueArgs lg{nets, pairs, n_actors, block / 32};
-  k_act_league32<<<G, kFwdThreads, kActMatchLds, st>>>(lg, a, c, mt);
-  if (hipGetLastError() != hipSuccess) return SK_EHIP;
-  k_episode_finish<<<1, 256, 0, st>>>(lengths, a.n, a.step, nullptr);
-  return hipGetLastError() == hipSuccess ? SK_OK : SK_EHIP;
+// a record (or none) of a launch of `blocks` blocks of `block` games
+static bool rec_ok(const sk_match_record* r, int64_t blocks, int64_t block) {
+  return !r || (r->per_block >= 1 && r->per_block <= block && r->rows == blocks * r->per_block);
 }
-
-// the recording twins (sk_env_act_match_rec / sk_env_act_league_rec, csrc/sk_engine.hip, which has checked the
-// record against the launch: rows, slabs, per_block, slab0 + n_ticks and every pointer)
 static RecArgs rec_args(const sk_match_record& r, int wgs_per_block) {
   return RecArgs{(int2*)r.states.pos,    (double*)r.states.rot,  (int2*)r.states.qpos, (double*)r.states.qrot,
                  (int2*)r.states.qcdage, (int2*)r.states.misc,   r.actions,            r.rewards,
                  (int64_t)r.rows,        r.per_block,            r.slab0,              wgs_per_block};
 }
-int sk_launch_act_match32_rec(const float* aflat1, const void* apack1, const float* aflat2, const void* apack2,
-                              const sk::StepArgs& a, const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths,
-                              int32_t* last_half, int n_ticks, const sk_match_record& rec, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    set_lds32(k_act_match32_rec, kActMatchLds);
-    attr = true;
-  }
-  if (!apack1 || !apack2 || ((((uintptr_t)apack1) | ((uintptr_t)apack2)) & 15)) return SK_EINVAL;
-  if (rec.per_block < 1 || rec.per_block > a.n || rec.rows != rec.per_block) return SK_EINVAL;
-  const unsigned G = (unsigned)((a.n + 31) / 32);
-  const MatchArgs mt{obs2, returns, lengths, last_half, n_ticks};
-  k_act_match32_rec<<<G, kFwdThreads, kActMatchLds, st>>>(aflat1, (const char*)apack1, aflat2, (const char*)apack2, a,
-                                                          c, mt, rec_args(rec, 0));
-  if (hipGetLastError() != hipSuccess) return SK_EHIP;
-  k_episode_finish<<<1, 256, 0, st>>>(lengths, a.n, a.step, nullptr);
-  return hipGetLastError() == hipSuccess ? SK_OK : SK_EHIP;
-}
-int sk_launch_act_league32_rec(const uint64_t* nets, int n_actors, const int32_t* pairs, int block,
-                               const sk::StepArgs& a, const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths,
-                               int32_t* last_half, int n_ticks, const sk_match_record& rec, hipStream_t st) {
-  static bool attr = false;
-  if (!attr) {
-    set_lds32(k_act_league32_rec, kActMatchLds);
-    attr = true;
-  }
-  if (!nets || !pairs || n_actors < 1 || block <= 0 || block % 32 || a.n % block) return SK_EINVAL;
-  if (rec.per_block < 1 || rec.per_block > block || rec.rows != (a.n / block) * rec.per_block) return SK_EINVAL;
-  const unsigned G = (unsigned)(a.n / 32);
-  const MatchArgs mt{obs2, returns, lengths, last_half, n_ticks};
-  const LeagueArgs lg{nets, pairs, n_actors, block / 32};
-  k_act_league32_rec<<<G, kFwdThreads, kActMatchLds, st>>>(lg, a, c, mt, rec_args(rec, block / 32));
+// behind a match kernel's launch: the step counter advances by max(lengths)
+static int match_finish(const sk::StepArgs& a, int32_t* lengths, hipStream_t st) {
   if (hipGetLastError() != hipSuccess) return SK_EHIP;
   k_episode_finish<<<1, 256, 0, st>>>(lengths, a.n, a.step, nullptr);
   return hipGetLastError() == hipSuccess ? SK_OK : SK_EHIP;
 }
 
-// the opponent-pool training tick (sk_env_act_step_pool, csrc/sk_engine.hip): a.n = n_pairs * block,
-// block % 32 == 0; nets / pairs are device tables
+// two actors' matches in one launch (sk_env_act_match / _rec): any a.n >= 1; rec: the record to keep, or NULL
+int sk_launch_act_match32(const float* aflat1, const void* apack1, const float* aflat2, const void* apack2,
+                          const sk::StepArgs& a, const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths,
+                          int32_t* last_half, int n_ticks, const sk_match_record* rec, hipStream_t st) {
+  static bool attr = false;
+  if (!attr) {
+    set_lds32(k_act_match32, kActMatchLds);
+    set_lds32(k_act_match32_rec, kActMatchLds);
+    attr = true;
+  }
+  if (!apack1 || !apack2 || ((((uintptr_t)apack1) | ((uintptr_t)apack2)) & 15)) return SK_EINVAL;
+  if (!rec_ok(rec, 1, a.n)) return SK_EINVAL;
+  const unsigned G = (unsigned)((a.n + 31) / 32);
+  const char *pk1 = (const char*)apack1, *pk2 = (const char*)apack2;
+  const MatchArgs mt{obs2, returns, lengths, last_half, n_ticks};
+  if (rec)
+    k_act_match32_rec<<<G, kFwdThreads, kActMatchLds, st>>>(aflat1, pk1, aflat2, pk2, a, c, mt, rec_args(*rec, 0));
+  else
+    k_act_match32<<<G, kFwdThreads, kActMatchLds, st>>>(aflat1, pk1, aflat2, pk2, a, c, mt);
+  return match_finish(a, lengths, st);
+}
+
+// every pairing of a league in one launch (sk_env_act_league / _rec): a seating, a record or NULL
+int sk_launch_act_league32(const uint64_t* nets, int n_actors, const int32_t* pairs, int block, const sk::StepArgs& a,
+                           const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
+                           int n_ticks, const sk_match_record* rec, hipStream_t st) {
+  static bool attr = false;
+  if (!attr) {
+    set_lds32(k_act_league32, kActMatchLds);
+    set_lds32(k_act_league32_rec, kActMatchLds);
+    attr = true;
+  }
+  if (!seating_ok(nets, n_actors, pairs, block, a) || !rec_ok(rec, a.n / block, block)) return SK_EINVAL;
+  const unsigned G = (unsigned)(a.n / 32);
+  const MatchArgs mt{obs2, returns, lengths, last_half, n_ticks};
+  const LeagueArgs lg{nets, pairs, n_actors, block / 32};
+  if (rec)
+    k_act_league32_rec<<<G, kFwdThreads, kActMatchLds, st>>>(lg, a, c, mt, rec_args(*rec, block / 32));
+  else
+    k_act_league32<<<G, kFwdThreads, kActMatchLds, st>>>(lg, a, c, mt);
+  return match_finish(a, lengths, st);
+}
+
+// the opponent-pool training tick (sk_env_act_step_pool): a seating
 int sk_launch_act_step_pool32(const uint64_t* nets, int n_actors, const int32_t* pairs, int block, int noisy_actor,
                               float* act_out, float sd, float action_sd, uint64_t seed, uint64_t* call_ctr,
                               const sk::StepArgs& a, const sk::Cfg& c, hipStream_t st) {
@@ -1224,7 +1206,7 @@ int sk_launch_act_step_pool32(const uint64_t* nets, int n_actors, const int32_t*
     set_lds32(k_act_step_pool32, kActPoolLds);
     attr = true;
   }
-  if (!nets || !pairs || !act_out || n_actors < 1 || block <= 0 || block % 32 || a.n % block) return SK_EINVAL;
+  if (!seating_ok(nets, n_actors, pairs, block, a) || !act_out) return SK_EINVAL;
   if (noisy_actor < -1 || noisy_actor >= n_actors) return SK_EINVAL;
   const unsigned G = (unsigned)(a.n / 32);
   const PoolArgs pl{nets, pairs, n_actors, block / 32, noisy_actor};

@@ -1179,52 +1179,36 @@ int sk_env_act_episode(sk_env* e, const float* actor_flat, const void* actor_pac
   return SK_OK;
 }
 
-int sk_env_act_match(sk_env* e, const float* actor1_flat, const void* actor1_pack, const float* actor2_flat,
-                     const void* actor2_pack, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
-                     int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, void* stream) {
-  SK_CHECK_ENV(e);
-  if (!actor1_flat || !actor2_flat || !actor1_pack || !actor2_pack || !obs2 || !lengths || n_ticks <= 0)
-    return fail(SK_EINVAL, "an actor's flat / pack, obs2 or lengths is NULL, or n_ticks <= 0");
-  if (e->host) return fail(SK_EINVAL, "sk_env_act_match runs on the GPU backend");
-  if ((((uintptr_t)actor1_pack) | ((uintptr_t)actor2_pack)) & 15)
-    return fail(SK_EINVAL, "actor1_pack / actor2_pack must be 16-byte aligned");
+// ---- sk_env_act_match / _league, their _rec twins and sk_env_act_step_pool refuse in one order (skillshot.h):
+// the handle, every argument, the record and last, with all of those in order, a CPU-backend handle.
+// the outputs of a match-shaped launch
+static int match_out_check(const float* obs2, const float* returns, const int32_t* lengths, const int32_t* last_half,
+                           int32_t n_ticks) {
+  if (!obs2 || !lengths || n_ticks <= 0) return fail(SK_EINVAL, "obs2 or lengths is NULL, or n_ticks <= 0");
   if ((((uintptr_t)lengths) | ((uintptr_t)returns) | ((uintptr_t)last_half)) & 3)
     return fail(SK_EINVAL, "lengths / returns / last_half must be 4-byte aligned");
-  StepArgs a;  // (checks obs2's 16-byte alignment and reward_kind; both halves are 96 N bytes apart)
-  int rc = act_step_args(e, obs2, nullptr, obs2, returns, reward_kind, nullptr, nullptr, tick_limit, 0, 0, nullptr,
-                         nullptr, 0, nullptr, nullptr, nullptr, a);
-  if (rc != SK_OK) return rc;
-  rc = sk_launch_act_match32(actor1_flat, actor1_pack, actor2_flat, actor2_pack, a, e->dcfg, obs2, returns, lengths,
-                             last_half, n_ticks, (hipStream_t)stream);
-  if (rc != SK_OK) return fail(rc, "k_act_match32 launch failed");
-  e->parity ^= 1;
+  if (((uintptr_t)obs2) & 15) return fail(SK_EINVAL, "obs2 must be 16-byte aligned");
   return SK_OK;
 }
 
-int sk_env_act_league(sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
-                      int32_t block, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
-                      int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, void* stream) {
-  SK_CHECK_ENV(e);
+// a seating: n_pairs blocks of `block` games, each acting from its pair of the n_actors rows of nets
+static int seating_check(const sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs,
+                         int32_t n_pairs, int32_t block) {
   if (!nets || !pairs) return fail(SK_EINVAL, "the nets or the pairs table is NULL");
-  if (!obs2 || !lengths || n_ticks <= 0) return fail(SK_EINVAL, "obs2 or lengths is NULL, or n_ticks <= 0");
   if (n_actors < 1 || n_pairs < 1) return fail(SK_EINVAL, "n_actors and n_pairs must be at least 1");
   if (block <= 0 || block % 32) return fail(SK_EINVAL, "block must be a positive multiple of 32");
   if ((int64_t)e->n != (int64_t)n_pairs * block) return fail(SK_EINVAL, "the env must hold n_pairs * block games");
   if ((((uintptr_t)nets) & 7) || (((uintptr_t)pairs) & 3))
     return fail(SK_EINVAL, "nets must be 8-byte aligned, pairs 4-byte");
-  if ((((uintptr_t)lengths) | ((uintptr_t)returns) | ((uintptr_t)last_half)) & 3)
-    return fail(SK_EINVAL, "lengths / returns / last_half must be 4-byte aligned");
-  if (((uintptr_t)obs2) & 15) return fail(SK_EINVAL, "obs2 must be 16-byte aligned");
-  if (e->host) return fail(SK_EINVAL, "sk_env_act_league runs on the GPU backend");
-  StepArgs a;  // (as sk_env_act_match)
-  int rc = act_step_args(e, obs2, nullptr, obs2, returns, reward_kind, nullptr, nullptr, tick_limit, 0, 0, nullptr,
-                         nullptr, 0, nullptr, nullptr, nullptr, a);
-  if (rc != SK_OK) return rc;
-  rc = sk_launch_act_league32(nets, n_actors, pairs, block, a, e->dcfg, obs2, returns, lengths, last_half, n_ticks,
-                              (hipStream_t)stream);
-  if (rc != SK_OK) return fail(rc, "k_act_league32 launch failed");
-  e->parity ^= 1;
   return SK_OK;
+}
+
+// a match's StepArgs (checks reward_kind): each tick acts on one half of obs2 and writes the other, the two
+// 96 N bytes apart; rewards into returns; no done / winner, no reset, no ring
+static int match_step_args(sk_env* e, float* obs2, float* returns, int32_t reward_kind, int32_t tick_limit,
+                           StepArgs& a) {
+  return act_step_args(e, obs2, nullptr, obs2, returns, reward_kind, nullptr, nullptr, tick_limit, 0, 0, nullptr,
+                       nullptr, 0, nullptr, nullptr, nullptr, a);
 }
 
 // a match record against its launch of `blocks` blocks of `block` games (include/skillshot.h)
@@ -1251,58 +1235,77 @@ static int rec_check(const sk_match_record* rec, int64_t blocks, int64_t block, 
   return SK_OK;
 }
 
+// sk_env_act_match (recording false: rec unused) and sk_env_act_match_rec
+static int act_match(sk_env* e, const float* actor1_flat, const void* actor1_pack, const float* actor2_flat,
+                     const void* actor2_pack, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
+                     int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, bool recording,
+                     const sk_match_record* rec, void* stream) {
+  SK_CHECK_ENV(e);
+  if (!actor1_flat || !actor2_flat || !actor1_pack || !actor2_pack)
+    return fail(SK_EINVAL, "an actor's flat or pack is NULL");
+  if ((((uintptr_t)actor1_pack) | ((uintptr_t)actor2_pack)) & 15)
+    return fail(SK_EINVAL, "actor1_pack / actor2_pack must be 16-byte aligned");
+  StepArgs a;  // (the checks in the family's order)
+  int rc = match_out_check(obs2, returns, lengths, last_half, n_ticks);
+  if (rc == SK_OK) rc = match_step_args(e, obs2, returns, reward_kind, tick_limit, a);
+  if (rc == SK_OK && recording) rc = rec_check(rec, 1, e->n, n_ticks, returns);
+  if (rc != SK_OK) return rc;
+  if (e->host) return fail(SK_EINVAL, "sk_env_act_match(_rec) runs on the GPU backend");
+  rc = sk_launch_act_match32(actor1_flat, actor1_pack, actor2_flat, actor2_pack, a, e->dcfg, obs2, returns, lengths,
+                             last_half, n_ticks, rec, (hipStream_t)stream);
+  if (rc != SK_OK) return fail(rc, "k_act_match32(_rec) launch failed");
+  e->parity ^= 1;
+  return SK_OK;
+}
+
+int sk_env_act_match(sk_env* e, const float* actor1_flat, const void* actor1_pack, const float* actor2_flat,
+                     const void* actor2_pack, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
+                     int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, void* stream) {
+  return act_match(e, actor1_flat, actor1_pack, actor2_flat, actor2_pack, obs2, returns, lengths, last_half, n_ticks,
+                   reward_kind, tick_limit, false, nullptr, stream);
+}
+
 int sk_env_act_match_rec(sk_env* e, const float* actor1_flat, const void* actor1_pack, const float* actor2_flat,
                          const void* actor2_pack, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
                          int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, const sk_match_record* rec,
                          void* stream) {
+  return act_match(e, actor1_flat, actor1_pack, actor2_flat, actor2_pack, obs2, returns, lengths, last_half, n_ticks,
+                   reward_kind, tick_limit, true, rec, stream);
+}
+
+// sk_env_act_league and sk_env_act_league_rec, as act_match
+static int act_league(sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
+                      int32_t block, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
+                      int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, bool recording,
+                      const sk_match_record* rec, void* stream) {
   SK_CHECK_ENV(e);
-  if (!actor1_flat || !actor2_flat || !actor1_pack || !actor2_pack || !obs2 || !lengths || n_ticks <= 0)
-    return fail(SK_EINVAL, "an actor's flat / pack, obs2 or lengths is NULL, or n_ticks <= 0");
-  if ((((uintptr_t)actor1_pack) | ((uintptr_t)actor2_pack)) & 15)
-    return fail(SK_EINVAL, "actor1_pack / actor2_pack must be 16-byte aligned");
-  if ((((uintptr_t)lengths) | ((uintptr_t)returns) | ((uintptr_t)last_half)) & 3)
-    return fail(SK_EINVAL, "lengths / returns / last_half must be 4-byte aligned");
-  int rc = rec_check(rec, 1, e->n, n_ticks, returns);
+  StepArgs a;
+  int rc = seating_check(e, nets, n_actors, pairs, n_pairs, block);
+  if (rc == SK_OK) rc = match_out_check(obs2, returns, lengths, last_half, n_ticks);
+  if (rc == SK_OK) rc = match_step_args(e, obs2, returns, reward_kind, tick_limit, a);
+  if (rc == SK_OK && recording) rc = rec_check(rec, n_pairs, block, n_ticks, returns);
   if (rc != SK_OK) return rc;
-  StepArgs a;  // (as sk_env_act_match)
-  rc = act_step_args(e, obs2, nullptr, obs2, returns, reward_kind, nullptr, nullptr, tick_limit, 0, 0, nullptr,
-                     nullptr, 0, nullptr, nullptr, nullptr, a);
-  if (rc != SK_OK) return rc;
-  if (e->host) return fail(SK_EINVAL, "sk_env_act_match_rec runs on the GPU backend");
-  rc = sk_launch_act_match32_rec(actor1_flat, actor1_pack, actor2_flat, actor2_pack, a, e->dcfg, obs2, returns,
-                                 lengths, last_half, n_ticks, *rec, (hipStream_t)stream);
-  if (rc != SK_OK) return fail(rc, "k_act_match32_rec launch failed");
+  if (e->host) return fail(SK_EINVAL, "sk_env_act_league(_rec) runs on the GPU backend");
+  rc = sk_launch_act_league32(nets, n_actors, pairs, block, a, e->dcfg, obs2, returns, lengths, last_half, n_ticks,
+                              rec, (hipStream_t)stream);
+  if (rc != SK_OK) return fail(rc, "k_act_league32(_rec) launch failed");
   e->parity ^= 1;
   return SK_OK;
+}
+
+int sk_env_act_league(sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
+                      int32_t block, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
+                      int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, void* stream) {
+  return act_league(e, nets, n_actors, pairs, n_pairs, block, obs2, returns, lengths, last_half, n_ticks, reward_kind,
+                    tick_limit, false, nullptr, stream);
 }
 
 int sk_env_act_league_rec(sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
                           int32_t block, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
                           int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, const sk_match_record* rec,
                           void* stream) {
-  SK_CHECK_ENV(e);
-  if (!nets || !pairs) return fail(SK_EINVAL, "the nets or the pairs table is NULL");
-  if (!obs2 || !lengths || n_ticks <= 0) return fail(SK_EINVAL, "obs2 or lengths is NULL, or n_ticks <= 0");
-  if (n_actors < 1 || n_pairs < 1) return fail(SK_EINVAL, "n_actors and n_pairs must be at least 1");
-  if (block <= 0 || block % 32) return fail(SK_EINVAL, "block must be a positive multiple of 32");
-  if ((int64_t)e->n != (int64_t)n_pairs * block) return fail(SK_EINVAL, "the env must hold n_pairs * block games");
-  if ((((uintptr_t)nets) & 7) || (((uintptr_t)pairs) & 3))
-    return fail(SK_EINVAL, "nets must be 8-byte aligned, pairs 4-byte");
-  if ((((uintptr_t)lengths) | ((uintptr_t)returns) | ((uintptr_t)last_half)) & 3)
-    return fail(SK_EINVAL, "lengths / returns / last_half must be 4-byte aligned");
-  if (((uintptr_t)obs2) & 15) return fail(SK_EINVAL, "obs2 must be 16-byte aligned");
-  int rc = rec_check(rec, n_pairs, block, n_ticks, returns);
-  if (rc != SK_OK) return rc;
-  if (e->host) return fail(SK_EINVAL, "sk_env_act_league_rec runs on the GPU backend");
-  StepArgs a;  // (as sk_env_act_match)
-  rc = act_step_args(e, obs2, nullptr, obs2, returns, reward_kind, nullptr, nullptr, tick_limit, 0, 0, nullptr,
-                     nullptr, 0, nullptr, nullptr, nullptr, a);
-  if (rc != SK_OK) return rc;
-  rc = sk_launch_act_league32_rec(nets, n_actors, pairs, block, a, e->dcfg, obs2, returns, lengths, last_half, n_ticks,
-                                  *rec, (hipStream_t)stream);
-  if (rc != SK_OK) return fail(rc, "k_act_league32_rec launch failed");
-  e->parity ^= 1;
-  return SK_OK;
+  return act_league(e, nets, n_actors, pairs, n_pairs, block, obs2, returns, lengths, last_half, n_ticks, reward_kind,
+                    tick_limit, true, rec, stream);
 }
 
 int sk_env_act_step_pool(sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
@@ -1312,20 +1315,16 @@ int sk_env_act_step_pool(sk_env* e, const uint64_t* nets, int32_t n_actors, cons
                          int32_t random_positions, float* obs_reset, float* ring, int64_t capacity, int64_t* total,
                          uint32_t* arrivals, int64_t* total_copy, void* stream) {
   SK_CHECK_ENV(e);
-  if (!nets || !pairs) return fail(SK_EINVAL, "the nets or the pairs table is NULL");
+  int rc = seating_check(e, nets, n_actors, pairs, n_pairs, block);
+  if (rc != SK_OK) return rc;
   if (!acting_obs || !actions) return fail(SK_EINVAL, "acting_obs / actions is NULL");
-  if (n_actors < 1 || n_pairs < 1) return fail(SK_EINVAL, "n_actors and n_pairs must be at least 1");
-  if (block <= 0 || block % 32) return fail(SK_EINVAL, "block must be a positive multiple of 32");
-  if ((int64_t)e->n != (int64_t)n_pairs * block) return fail(SK_EINVAL, "the env must hold n_pairs * block games");
   if (noisy_actor < -1 || noisy_actor >= n_actors) return fail(SK_EINVAL, "noisy_actor must lie in [-1, n_actors)");
-  if ((((uintptr_t)nets) & 7) || (((uintptr_t)pairs) & 3))
-    return fail(SK_EINVAL, "nets must be 8-byte aligned, pairs 4-byte");
   if ((((uintptr_t)actions) & 7) || (((uintptr_t)acting_obs) & 15))
     return fail(SK_EINVAL, "actions must be 8-byte aligned, acting_obs 16-byte");
   if (((uintptr_t)call_counter) & 7) return fail(SK_EINVAL, "call_counter must be 8-byte aligned");
   StepArgs a;
-  int rc = act_step_args(e, acting_obs, actions, obs, reward, reward_kind, done, winner, tick_limit, auto_reset,
-                         random_positions, obs_reset, ring, capacity, total, arrivals, total_copy, a);
+  rc = act_step_args(e, acting_obs, actions, obs, reward, reward_kind, done, winner, tick_limit, auto_reset,
+                     random_positions, obs_reset, ring, capacity, total, arrivals, total_copy, a);
   if (rc != SK_OK) return rc;
   if (e->host) return fail(SK_EINVAL, "sk_env_act_step_pool runs on the GPU backend");
   rc = sk_launch_act_step_pool32(nets, n_actors, pairs, block, noisy_actor, actions, noise_sd, action_sd, noise_seed,

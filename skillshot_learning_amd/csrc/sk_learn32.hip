@@ -2,7 +2,9 @@
 // and fp32 accumulation, for the Keras fp32 nets of SkillshotLearner.py:70-121
 // and their update (:386-443).  This file holds the gradient half and the C
 // entry points; the acting half (the actor forward, the self-play tick, the
-// episode, match and league kernels and their launchers) is sk_act32.hpp,
+// episode, match, league, recording and pool-tick kernels and their launchers,
+// one per kernel family: a recording twin is launched by its plain kernel's
+// launcher, given a match record) is sk_act32.hpp,
 // included below into this translation unit, and what both halves share
 // (the nets' views, Philox, the MFMA fragments, the size constants) is
 // sk_net32.hpp.

@@ -506,21 +506,15 @@ int sk_launch_act_step32(const float* aflat, const void* apack, float* act_out, 
 int sk_launch_act_episode32(const float* aflat, const void* apack, float sd, float action_sd, uint64_t seed,
                             uint64_t* call_ctr, const sk::StepArgs& a, const sk::Cfg& c, float* states,
                             float* actions, float* rewards, int32_t* lengths, int n_ticks, hipStream_t st);
-// k_act_match32 (csrc/sk_act32.hpp): two actors' whole matches, one launch
+// k_act_match32 / k_act_match32_rec (csrc/sk_act32.hpp): two actors' whole matches, one launch; rec: the match
+// record to keep, or NULL
 int sk_launch_act_match32(const float* aflat1, const void* apack1, const float* aflat2, const void* apack2,
                           const sk::StepArgs& a, const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths,
-                          int32_t* last_half, int n_ticks, hipStream_t st);
-// k_act_league32 (csrc/sk_act32.hpp): every pairing of K actors, whole matches, one launch
+                          int32_t* last_half, int n_ticks, const sk_match_record* rec, hipStream_t st);
+// k_act_league32 / k_act_league32_rec (csrc/sk_act32.hpp): every pairing of K actors, whole matches, one launch
 int sk_launch_act_league32(const uint64_t* nets, int n_actors, const int32_t* pairs, int block, const sk::StepArgs& a,
                            const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
-                           int n_ticks, hipStream_t st);
-// k_act_match32_rec / k_act_league32_rec (csrc/sk_act32.hpp): the two above, keeping the match record `rec`
-int sk_launch_act_match32_rec(const float* aflat1, const void* apack1, const float* aflat2, const void* apack2,
-                              const sk::StepArgs& a, const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths,
-                              int32_t* last_half, int n_ticks, const sk_match_record& rec, hipStream_t st);
-int sk_launch_act_league32_rec(const uint64_t* nets, int n_actors, const int32_t* pairs, int block,
-                               const sk::StepArgs& a, const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths,
-                               int32_t* last_half, int n_ticks, const sk_match_record& rec, hipStream_t st);
+                           int n_ticks, const sk_match_record* rec, hipStream_t st);
 // k_act_step_pool32 (csrc/sk_act32.hpp): the pool training tick, each block of games acting from its pairing's actors
 int sk_launch_act_step_pool32(const uint64_t* nets, int n_actors, const int32_t* pairs, int block, int noisy_actor,
                               float* act_out, float sd, float action_sd, uint64_t seed, uint64_t* call_ctr,

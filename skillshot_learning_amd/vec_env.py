@@ -393,19 +393,19 @@ class VecSkillshotGame:
         ring.total += 2 * self.n  # host mirror (exact while the row count is fixed)
         return dict(obs=obs_t, reward=rew_t, done=done, winner=win, obs_reset=obs_r)
 
-    def act_step(self, actor, acting_obs, noise_sd=0.0, action_sd=0.0, ring=None, reward="looking", auto_reset=True,
-                 reset_obs=True, out=None, actions=None, total_copy=None, job=None):
-        """The self-play tick's act + step (+ ring insert) in ONE launch
-        (sk_env_act_step): `actor` (actor_kernel.ActorKernel32, the fp32
-        actor) acts on acting_obs [2, N, 12] for both players of every game
-        with parameter noise noise_sd and/or action noise action_sd, and the
-        step runs on those actions; equal, bit for bit, to actor(...) with
-        32-row tiles followed by step_insert (ring given; total_copy as
-        step_insert's) or step.  job (_capi.SkStepJob): prepare the launch
-        into it instead (sk_env_act_step_job; run by the actor step's
-        backward launch, update_kernel.actor_step(step_job=job)).  Returns
-        step's dict plus `actions` [2, N, 2]."""
-        o = out or {}
+    def _out_buf(self, o, key, shape, dtype):
+        """o[key], checked (contiguous `dtype` `shape` on this device), or a new tensor when `o` has none"""
+        t = o.get(key)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=self.device)
+        elif tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+            raise ValueError(f"out[{key!r}] must be contiguous {dtype} {shape} on {self.device}")
+        return t
+
+    def _act_step_out(self, o, acting_obs, actions, reset_obs, ring, total_copy):
+        """what act_step and act_step_pool share: the dict they return (the
+        tick's outputs, taken from `o` where it has them), the acting rows as
+        the launch reads them and the ring's five C arguments"""
         obs_t = o.get("obs") if o.get("obs") is not None else self.new_obs()
         rew_t = o.get("reward") if o.get("reward") is not None else torch.empty((2, self.n), dtype=torch.float32,
                                                                                 device=self.device)
@@ -420,17 +420,33 @@ class VecSkillshotGame:
             raise ValueError("acting_obs must hold [2, N, 12] floats, actions [2, N, 2] (contiguous)")
         ring_args = ((_ptr(ring.buf), ring.cap, _ptr(ring.total_t), _ptr(ring.arrivals()), _ptr(total_copy))
                      if ring is not None else (None, 0, None, None, None))
+        return dict(obs=obs_t, reward=rew_t, done=done, winner=win, obs_reset=obs_r, actions=act), s, ring_args
+
+    def act_step(self, actor, acting_obs, noise_sd=0.0, action_sd=0.0, ring=None, reward="looking", auto_reset=True,
+                 reset_obs=True, out=None, actions=None, total_copy=None, job=None):
+        """The self-play tick's act + step (+ ring insert) in ONE launch
+        (sk_env_act_step): `actor` (actor_kernel.ActorKernel32, the fp32
+        actor) acts on acting_obs [2, N, 12] for both players of every game
+        with parameter noise noise_sd and/or action noise action_sd, and the
+        step runs on those actions; equal, bit for bit, to actor(...) with
+        32-row tiles followed by step_insert (ring given; total_copy as
+        step_insert's) or step.  job (_capi.SkStepJob): prepare the launch
+        into it instead (sk_env_act_step_job; run by the actor step's
+        backward launch, update_kernel.actor_step(step_job=job)).  Returns
+        step's dict plus `actions` [2, N, 2]."""
+        res, s, ring_args = self._act_step_out(out or {}, acting_obs, actions, reset_obs, ring, total_copy)
         pack = actor.ensure_pack()
-        args = (self._h, _ptr(actor.flat), _ptr(pack), _ptr(s), _ptr(act), float(noise_sd), float(action_sd), actor.seed,
-                _ptr(actor._ctr), _ptr(obs_t), _ptr(rew_t), REWARD_KINDS[reward], _ptr(done), _ptr(win),
-                self.tick_limit, int(bool(auto_reset)), int(self.random_positions), _ptr(obs_r), *ring_args)
+        args = (self._h, _ptr(actor.flat), _ptr(pack), _ptr(s), _ptr(res["actions"]), float(noise_sd),
+                float(action_sd), actor.seed, _ptr(actor._ctr), _ptr(res["obs"]), _ptr(res["reward"]),
+                REWARD_KINDS[reward], _ptr(res["done"]), _ptr(res["winner"]), self.tick_limit, int(bool(auto_reset)),
+                int(self.random_positions), _ptr(res["obs_reset"]), *ring_args)
         if job is not None:
             check(self._L.sk_env_act_step_job(*args, ctypes.byref(job)))
         else:
             check(self._L.sk_env_act_step(*args, self._stream()))
         if ring is not None:
             ring.total += 2 * self.n  # host mirror
-        return dict(obs=obs_t, reward=rew_t, done=done, winner=win, obs_reset=obs_r, actions=act)
+        return res
 
     def act_episode(self, actor, start_obs, n_ticks=None, noise_sd=0.0, action_sd=0.0, reward="looking",
                     out=None):
@@ -496,15 +512,14 @@ class VecSkillshotGame:
                 raise ValueError(f"pair ({i}, {j}) names an actor outside [0, {len(actors)})")
         return actors, plist, block
 
-    @staticmethod
-    def _seating_tables(actors, plist, o, buf):
+    def _seating_tables(self, actors, plist, o):
         """the two device tables of a seating (the actors' addresses, the
         pairs), taken from the dict `o` of an earlier call and uploaded only
         when the actors' buffers or the pairs differ from that call's:
         (nets, pairs, the key to keep as `tables`)"""
         addr = tuple((a.flat.data_ptr(), a.ensure_pack().data_ptr()) for a in actors)
-        nets = buf("nets", (len(actors), 2), torch.int64)
-        prs = buf("pairs", (len(plist), 2), torch.int32)
+        nets = self._out_buf(o, "nets", (len(actors), 2), torch.int64)
+        prs = self._out_buf(o, "pairs", (len(plist), 2), torch.int32)
         if o.get("tables") != (addr, plist) or nets is not o.get("nets") or prs is not o.get("pairs"):
             nets.copy_(torch.tensor(addr, dtype=torch.int64))
             prs.copy_(torch.tensor(plist, dtype=torch.int32))
@@ -534,6 +549,47 @@ class VecSkillshotGame:
         if not resume:
             rec.ticks_run = 0
         return rec
+
+    def _match_launch(self, what, plain, recording, seats, blocks, block, start_obs, n_ticks, reward, o, resume,
+                      record):
+        """act_match's / act_league's launch over `blocks` blocks of `block`
+        games: the C symbol `plain`, or `recording` (plain's arguments and the
+        record) while the record has slabs left, with the seating's arguments
+        `seats` between the handle and the shared ones.  Returns act_match's
+        dict."""
+        if resume and (o.get("returns") is None or o.get("lengths") is None):
+            raise ValueError(f"resume needs the dict a previous {what} returned as out")
+        T = int(self.tick_limit if n_ticks is None else n_ticks)
+        start = start_obs.reshape(2, self.n, 12)  # (may be out["obs"]: read before it is rewritten)
+        obs2 = self._out_buf(o, "obs2", (2, 2, self.n, 12), torch.float32)
+        ret = self._out_buf(o, "returns", (2, self.n), torch.float32)
+        call_ln = self._out_buf(o, "call_lengths", (self.n,), torch.int32)
+        total = self._out_buf(o, "lengths", (self.n,), torch.int32)
+        obs = self._out_buf(o, "obs", (2, self.n, 12), torch.float32)
+        obs2[0].copy_(start)
+        if not resume:
+            ret.zero_()
+        rec = self._match_record(record, blocks, block, resume)
+        T_rec = min(T, rec.slabs - 1 - rec.ticks_run) if rec is not None else 0
+        outs = (_ptr(obs2), _ptr(ret), _ptr(call_ln), _ptr(o.get("last_half")))
+        if T_rec >= 1:
+            st = rec.c_struct(rec.ticks_run)
+            check(recording(self._h, *seats, *outs, T_rec, REWARD_KINDS[reward], self.tick_limit, ctypes.byref(st),
+                            self._stream()))
+            rec.ticks_run += T_rec
+        else:
+            check(plain(self._h, *seats, *outs, T, REWARD_KINDS[reward], self.tick_limit, self._stream()))
+        torch.where((call_ln & 1).bool()[None, :, None], obs2[1], obs2[0], out=obs)
+        if resume:
+            total += call_ln
+        else:
+            total.copy_(call_ln)
+        res = dict(lengths=total, returns=ret, obs=obs, obs2=obs2, call_lengths=call_ln,
+                   last_half=o.get("last_half"))
+        if rec is not None:
+            torch.index_select(total, 0, rec.games, out=rec.lengths)
+            res["record"] = rec
+        return res
 
     def act_match(self, actor1, actor2, start_obs, n_ticks=None, reward="looking", out=None, resume=False,
                   record=None):
@@ -565,53 +621,9 @@ class VecSkillshotGame:
         has slabs left for; once they are used up the call runs unrecorded."""
         if self.is_cpu:
             raise SkillshotError("act_match runs on the GPU backend (SkillshotLearner.evaluate loops on the CPU one)")
-        T = int(self.tick_limit if n_ticks is None else n_ticks)
-        o = out or {}
-        if resume and (o.get("returns") is None or o.get("lengths") is None):
-            raise ValueError("resume needs the dict a previous act_match returned as out")
-
-        def buf(key, shape, dtype):
-            t = o.get(key)
-            if t is None:
-                t = torch.empty(shape, dtype=dtype, device=self.device)
-            elif tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"out[{key!r}] must be contiguous {dtype} {shape} on {self.device}")
-            return t
-
-        start = start_obs.reshape(2, self.n, 12)  # (may be out["obs"]: read before it is rewritten)
-        obs2 = buf("obs2", (2, 2, self.n, 12), torch.float32)
-        ret = buf("returns", (2, self.n), torch.float32)
-        call_ln = buf("call_lengths", (self.n,), torch.int32)
-        total = buf("lengths", (self.n,), torch.int32)
-        obs = buf("obs", (2, self.n, 12), torch.float32)
-        obs2[0].copy_(start)
-        if not resume:
-            ret.zero_()
-        p1, p2 = actor1.ensure_pack(), actor2.ensure_pack()
-        rec = self._match_record(record, 1, self.n, resume)
-        T_rec = min(T, rec.slabs - 1 - rec.ticks_run) if rec is not None else 0
-        if T_rec >= 1:
-            st = rec.c_struct(rec.ticks_run)
-            check(self._L.sk_env_act_match_rec(self._h, _ptr(actor1.flat), _ptr(p1), _ptr(actor2.flat), _ptr(p2),
-                                               _ptr(obs2), _ptr(ret), _ptr(call_ln), _ptr(o.get("last_half")), T_rec,
-                                               REWARD_KINDS[reward], self.tick_limit, ctypes.byref(st),
-                                               self._stream()))
-            rec.ticks_run += T_rec
-        else:
-            check(self._L.sk_env_act_match(self._h, _ptr(actor1.flat), _ptr(p1), _ptr(actor2.flat), _ptr(p2),
-                                           _ptr(obs2), _ptr(ret), _ptr(call_ln), _ptr(o.get("last_half")), T,
-                                           REWARD_KINDS[reward], self.tick_limit, self._stream()))
-        torch.where((call_ln & 1).bool()[None, :, None], obs2[1], obs2[0], out=obs)
-        if resume:
-            total += call_ln
-        else:
-            total.copy_(call_ln)
-        res = dict(lengths=total, returns=ret, obs=obs, obs2=obs2, call_lengths=call_ln,
-                   last_half=o.get("last_half"))
-        if rec is not None:
-            torch.index_select(total, 0, rec.games, out=rec.lengths)
-            res["record"] = rec
-        return res
+        seats = (_ptr(actor1.flat), _ptr(actor1.ensure_pack()), _ptr(actor2.flat), _ptr(actor2.ensure_pack()))
+        return self._match_launch("act_match", self._L.sk_env_act_match, self._L.sk_env_act_match_rec, seats, 1,
+                                  self.n, start_obs, n_ticks, reward, out or {}, resume, record)
 
     def act_league(self, actors, pairs, block, start_obs, n_ticks=None, reward="looking", out=None, resume=False,
                    record=None):
@@ -635,52 +647,13 @@ class VecSkillshotGame:
             raise SkillshotError("act_league runs on the GPU backend (SkillshotLearner.league loops on the CPU one)")
         o = out or {}
         actors, plist, block = self._seating("act_league", actors, pairs, block, o)
-        T = int(self.tick_limit if n_ticks is None else n_ticks)
-        if resume and (o.get("returns") is None or o.get("lengths") is None):
-            raise ValueError("resume needs the dict a previous act_league returned as out")
-
-        def buf(key, shape, dtype):
-            t = o.get(key)
-            if t is None:
-                t = torch.empty(shape, dtype=dtype, device=self.device)
-            elif tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"out[{key!r}] must be contiguous {dtype} {shape} on {self.device}")
-            return t
-
-        nets, prs, tables = self._seating_tables(actors, plist, o, buf)
-        start = start_obs.reshape(2, self.n, 12)  # (may be out["obs"]: read before it is rewritten)
-        obs2 = buf("obs2", (2, 2, self.n, 12), torch.float32)
-        ret = buf("returns", (2, self.n), torch.float32)
-        call_ln = buf("call_lengths", (self.n,), torch.int32)
-        total = buf("lengths", (self.n,), torch.int32)
-        obs = buf("obs", (2, self.n, 12), torch.float32)
-        obs2[0].copy_(start)
-        if not resume:
-            ret.zero_()
-        rec = self._match_record(record, len(plist), block, resume)
-        T_rec = min(T, rec.slabs - 1 - rec.ticks_run) if rec is not None else 0
-        if T_rec >= 1:
-            st = rec.c_struct(rec.ticks_run)
-            check(self._L.sk_env_act_league_rec(self._h, _ptr(nets), len(actors), _ptr(prs), len(plist), block,
-                                                _ptr(obs2), _ptr(ret), _ptr(call_ln), _ptr(o.get("last_half")), T_rec,
-                                                REWARD_KINDS[reward], self.tick_limit, ctypes.byref(st),
-                                                self._stream()))
-            rec.ticks_run += T_rec
-        else:
-            check(self._L.sk_env_act_league(self._h, _ptr(nets), len(actors), _ptr(prs), len(plist), block,
-                                            _ptr(obs2), _ptr(ret), _ptr(call_ln), _ptr(o.get("last_half")), T,
-                                            REWARD_KINDS[reward], self.tick_limit, self._stream()))
-        torch.where((call_ln & 1).bool()[None, :, None], obs2[1], obs2[0], out=obs)
-        if resume:
-            total += call_ln
-        else:
-            total.copy_(call_ln)
-        res = dict(lengths=total, returns=ret, obs=obs, obs2=obs2, call_lengths=call_ln,
-                   last_half=o.get("last_half"), nets=nets, pairs=prs, tables=tables)
-        if rec is not None:
-            torch.index_select(total, 0, rec.games, out=rec.lengths)
-            rec.pairs = [plist[p] for p in range(len(plist)) for _ in range(rec.per_block)]
-            res["record"] = rec
+        nets, prs, tables = self._seating_tables(actors, plist, o)
+        seats = (_ptr(nets), len(actors), _ptr(prs), len(plist), block)
+        res = self._match_launch("act_league", self._L.sk_env_act_league, self._L.sk_env_act_league_rec, seats,
+                                 len(plist), block, start_obs, n_ticks, reward, o, resume, record)
+        res.update(nets=nets, pairs=prs, tables=tables)
+        if "record" in res:
+            res["record"].pairs = [plist[p] for p in range(len(plist)) for _ in range(res["record"].per_block)]
         return res
 
     def act_step_pool(self, actors, pairs, block, acting_obs, noisy=None, noise_sd=0.0, action_sd=0.0, ring=None,
@@ -711,41 +684,20 @@ class VecSkillshotGame:
             raise ValueError(f"noisy must be None or an actor index in [0, {len(actors)})")
         if noisy is None and (noise_sd != 0.0 or action_sd != 0.0):
             raise ValueError("noise_sd / action_sd need the noisy actor's index")
-
-        def buf(key, shape, dtype):
-            t = o.get(key)
-            if t is None:
-                t = torch.empty(shape, dtype=dtype, device=self.device)
-            elif tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"out[{key!r}] must be contiguous {dtype} {shape} on {self.device}")
-            return t
-
-        nets, prs, tables = self._seating_tables(actors, plist, o, buf)
-        obs_t = o.get("obs") if o.get("obs") is not None else self.new_obs()
-        rew_t = o.get("reward") if o.get("reward") is not None else torch.empty((2, self.n), dtype=torch.float32,
-                                                                                device=self.device)
-        done = o.get("done") if o.get("done") is not None else torch.empty(self.n, dtype=torch.uint8,
-                                                                            device=self.device)
-        win = o.get("winner") if o.get("winner") is not None else torch.empty(self.n, dtype=torch.uint8,
-                                                                               device=self.device)
-        obs_r = (o.get("obs_reset") if o.get("obs_reset") is not None else self.new_obs()) if reset_obs else None
-        act = actions if actions is not None else torch.empty((2, self.n, 2), dtype=torch.float32, device=self.device)
-        s = acting_obs.float().contiguous()
-        if s.numel() != 2 * self.n * 12 or act.numel() != 4 * self.n or not act.is_contiguous():
-            raise ValueError("acting_obs must hold [2, N, 12] floats, actions [2, N, 2] (contiguous)")
-        ring_args = ((_ptr(ring.buf), ring.cap, _ptr(ring.total_t), _ptr(ring.arrivals()), _ptr(total_copy))
-                     if ring is not None else (None, 0, None, None, None))
+        nets, prs, tables = self._seating_tables(actors, plist, o)
+        res, s, ring_args = self._act_step_out(o, acting_obs, actions, reset_obs, ring, total_copy)
         learner = actors[int(noisy)] if noisy is not None else None
         check(self._L.sk_env_act_step_pool(
             self._h, _ptr(nets), len(actors), _ptr(prs), len(plist), block, -1 if noisy is None else int(noisy),
-            _ptr(s), _ptr(act), float(noise_sd), float(action_sd), learner.seed if learner is not None else 0,
-            _ptr(learner._ctr) if learner is not None else None, _ptr(obs_t), _ptr(rew_t), REWARD_KINDS[reward],
-            _ptr(done), _ptr(win), self.tick_limit, int(bool(auto_reset)), int(self.random_positions), _ptr(obs_r),
-            *ring_args, self._stream()))
+            _ptr(s), _ptr(res["actions"]), float(noise_sd), float(action_sd),
+            learner.seed if learner is not None else 0, _ptr(learner._ctr) if learner is not None else None,
+            _ptr(res["obs"]), _ptr(res["reward"]), REWARD_KINDS[reward], _ptr(res["done"]), _ptr(res["winner"]),
+            self.tick_limit, int(bool(auto_reset)), int(self.random_positions), _ptr(res["obs_reset"]), *ring_args,
+            self._stream()))
         if ring is not None:
             ring.total += 2 * self.n  # host mirror
-        return dict(obs=obs_t, reward=rew_t, done=done, winner=win, obs_reset=obs_r, actions=act, nets=nets,
-                    pairs=prs, tables=tables)
+        res.update(nets=nets, pairs=prs, tables=tables)
+        return res
 
     def step_raw(self, actions_ptr, done_ptr=None, obs_ptr=None, reward_ptr=None, winner_ptr=None,
                  auto_reset=True, stream=None):

@@ -165,6 +165,13 @@ def test_act_match_refuses_the_cpu_backend_and_bad_arguments():
     assert b"lengths" in lib.sk_last_error()
     assert lib.sk_env_act_match(h, buf, buf, buf, buf, buf, buf, ln, None, 0, 0, 2000, None) == _capi.SK_EINVAL
     assert b"n_ticks" in lib.sk_last_error()
+    # two faults: a bad argument is reported ahead of the CPU backend (as sk_env_act_league does)
+    odd = ctypes.c_void_p(ctypes.addressof(ln) + 1)
+    assert lib.sk_env_act_match(h, buf, buf, buf, buf, buf, buf, odd, None, 10, 0, 2000, None) == _capi.SK_EINVAL
+    assert b"aligned" in lib.sk_last_error() and b"GPU" not in lib.sk_last_error()
+    pack8 = ctypes.c_void_p(ctypes.addressof(buf) + 8)
+    assert lib.sk_env_act_match(h, buf, buf, buf, pack8, buf, buf, ln, None, 10, 0, 2000, None) == _capi.SK_EINVAL
+    assert b"aligned" in lib.sk_last_error() and b"GPU" not in lib.sk_last_error()
     assert lib.sk_env_act_match(None, buf, buf, buf, buf, buf, buf, ln, None, 10, 0, 2000, None) == _capi.SK_EINVAL
     assert lib.sk_env_destroy(h) == _capi.SK_OK
     g = ssa.VecSkillshotGame(4, device="cpu")

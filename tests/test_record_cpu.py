@@ -103,6 +103,11 @@ def test_recording_entry_points_resolve_and_refuse_bad_arguments():
                                         None if rec is None else ctypes.byref(rec), None)
 
     refusals(match, bufs, 8, T)
+    # two faults: the record, and a bad argument ahead of it, are reported ahead of the CPU backend
+    assert match(bufs.with_(per_block=0)) == _capi.SK_EINVAL
+    assert b"per_block" in lib.sk_last_error() and b"GPU" not in lib.sk_last_error()
+    assert match(bufs.with_(per_block=0), lengths=ctypes.c_void_p(ctypes.addressof(ln) + 1)) == _capi.SK_EINVAL
+    assert b"aligned" in lib.sk_last_error()
     assert match(bufs.rec, returns=None) == _capi.SK_EINVAL and b"returns" in lib.sk_last_error()
     assert match(bufs.with_(rewards=None), returns=None) == _capi.SK_EINVAL and b"GPU" in lib.sk_last_error()
     assert match(bufs.rec, lengths=None) == _capi.SK_EINVAL and b"lengths" in lib.sk_last_error()  # the plain twin's
