@@ -18,8 +18,11 @@
 //                         time (split_tick_carry's STEADY form), 32-bit
 //                         offsets into the ring and the output rows, and
 //                         (FAST) the tick's state-independent arithmetic
-//                         under its loads (SplitPre) and a rest between its
-//                         stores and its reload
+//                         under its loads (SplitPre), there also the lanes
+//                         that may need the exact evaluation
+//                         (split_pre_maybe: the exactness guard is one
+//                         scalar branch behind the state wait), and a rest
+//                         between its stores and its reload
 //     both run the carried-sincos tick: tick_env_carry (sk_device.hpp) and
 //     split_tick_carry (below)
 //
@@ -864,9 +867,14 @@ __device__ __forceinline__ void split_store_pack_word(const MultiArgs& a, __amdg
 // (kSteadyRest).  A hit makes the game `done`: inside the `any_done` block a
 // game hit in this tick that does not restart stores its {pos, cah} word
 // again (a restarting one all three planes, as before), after the first store
-// in program order, from the same lane to the same address.  From the state
-// wait to the last state store the full-wave tick has 113 instructions on its
-// common path for 146 (profiles/r16_listing.txt), and that stretch runs at
+// in program order, from the same lane to the same address.  The FAST steady
+// tick decides the exactness guard under its loads: `maybe`, the lanes with
+// !msafe || !qsafe || qex, all known before the state arrives (SplitPre, the
+// carry), is a superset of `un` lane by lane, so behind the wait a wave-tick
+// where `maybe` is empty (all but about one in two hundred) takes one scalar
+// branch, and only the others evaluate `un` and its ballot.  From the state
+// wait to the last state store the full-wave tick has 102 instructions on its
+// common path for 113 (profiles/r20_listing.txt), and that stretch runs at
 // issue priority 1 (kSteadyPrio).
 //
 // FULL (STEADY only): every lane of the wave is in range, `L.in` is true at
@@ -881,6 +889,7 @@ struct SplitSteady {
   __amdgpu_buffer_rsrc_t ra, rd, rw;  // the action ring, done, winner (a NULL output: no records, its stores are dropped)
   uint32_t va, vd;                    // this lane's byte offset in an action slab / an output row
   uint32_t aso, dso;                  // the next tick's slab and this tick's output row, in bytes (wave-uniform)
+  unsigned long long maybe;           // FAST: the lanes that may need the exact evaluation this tick (split_pre_maybe)
 };
 // The part of the FAST tick that reads no loaded state, only the carried
 // sincos_fast of the rotation, the action and the configuration: the clamped
@@ -919,12 +928,30 @@ __device__ __forceinline__ SplitPre split_fast_pre(const sktrig::SinCosF& m, boo
   return q;
 }
 // (the two decisions are pinned as the lane masks they are: every lane of the
-// wave is active where the steady loop evaluates them)
-__device__ __forceinline__ void split_pre_pin(SplitPre& q) {
+// wave is active where the steady loop evaluates them; returns the lanes with
+// a decision that is not safe, off the pinned masks: split_pre_unsafe)
+__device__ __forceinline__ unsigned long long split_pre_pin(SplitPre& q) {
   unsigned long long ms = __builtin_amdgcn_ballot_w64(q.msafe), qs = __builtin_amdgcn_ballot_w64(q.qsafe);
   asm volatile("" : "+v"(q.dl), "+v"(q.imx), "+v"(q.imy), "+v"(q.iex), "+v"(q.iey), "+s"(ms), "+s"(qs));
   q.msafe = __builtin_amdgcn_inverse_ballot_w64(ms);
   q.qsafe = __builtin_amdgcn_inverse_ballot_w64(qs);
+  return ~(ms & qs);
+}
+// The lanes whose tick may need the exact evaluation, from what is known
+// before the state arrives: `un` of the tick is !msafe || (f && !qsafe) ||
+// (qvalid && !f && qex), so lane by lane un implies !msafe || !qsafe || qex,
+// whatever f and qvalid turn out to be.  `unsafe`: the lanes with !msafe ||
+// !qsafe; `in`: the lanes in range.  An SGPR pair, nonzero in 0.48 % of the
+// benchmark's wave-ticks.
+__device__ __forceinline__ unsigned long long split_pre_maybe(unsigned long long unsafe, bool qex,
+                                                              unsigned long long in) {
+  unsigned long long m = (unsafe | __builtin_amdgcn_ballot_w64(qex)) & in;
+  asm volatile("" : "+s"(m));
+  return m;
+}
+// ... the lanes with a decision of `q` that is not safe (the key-miss block's refreshed SplitPre)
+__device__ __forceinline__ unsigned long long split_pre_unsafe(const SplitPre& q) {
+  return ~(__builtin_amdgcn_ballot_w64(q.msafe) & __builtin_amdgcn_ballot_w64(q.qsafe));
 }
 template <int POL, bool OBS, bool PACK = false, bool FAST = false, bool STEADY = false, bool FULL = false>
 __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& c, __amdgpu_buffer_rsrc_t r,
@@ -932,7 +959,7 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
                                                  const SplitRaw& w, float2 act,
                                                  typename SplitCarrySel<FAST>::type& tc, bool last,
                                                  __amdgpu_buffer_rsrc_t rp, bool& packed,
-                                                 const SplitSteady* ss = nullptr, SplitPre* pre = nullptr,
+                                                 SplitSteady* ss = nullptr, SplitPre* pre = nullptr,
                                                  int left = 0, bool* admit = nullptr) {
   constexpr bool PRE = FAST && STEADY;  // the state-independent part arrives evaluated (SplitPre)
   static_assert(!(OBS && PACK), "the full contract never packs");
@@ -981,7 +1008,10 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
     tc.kr = rot;
     tc.kq = qrot;
     tc.have = true;
-    if constexpr (PRE) *pre = split_fast_pre(tc.m, tc.mok, act, c);  // off the refreshed carry
+    if constexpr (PRE) {  // off the refreshed carry
+      *pre = split_fast_pre(tc.m, tc.mok, act, c);
+      ss->maybe = split_pre_maybe(split_pre_unsafe(*pre), tc.qex, FULL ? ~0ull : __builtin_amdgcn_ballot_w64(in));
+    }
   }
   SplitPre q{};
   if constexpr (PRE) q = *pre;
@@ -1000,8 +1030,8 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
   if constexpr (PRE) {
     mdx = q.mdx;
     mdy = q.mdy;
-    unq = f && !q.qsafe;
-    un = !q.msafe || unq || (qvalid && !f && tc.qex);
+    unq = (int)f & (int)!q.qsafe;
+    un = false;  // (decided below, and only in a wave-tick where some lane may: ss->maybe)
   } else if constexpr (FAST) {
     const sktrig::FastDelta dm = sktrig::fast_move_delta(tc.m, tc.mok, (float)c.pspeed, clamp_action_f(act.x));
     mdx = dm.x;
@@ -1031,7 +1061,19 @@ __device__ __forceinline__ void split_tick_carry(const MultiArgs& a, const Cfg& 
       }
     }
   }
-  if (__builtin_expect(__ballot(in && un) != 0, 0)) {  // the exact sincos of the fired projectiles
+  bool any_un;  // wave-uniform
+  if constexpr (PRE) {
+    // un is a subset of ss->maybe lane by lane (split_pre_maybe), so a wave-tick
+    // where nothing may takes one scalar branch here, no mask arithmetic
+    any_un = false;
+    if (__builtin_expect(ss->maybe != 0, 0)) {
+      un = (int)!q.msafe | (int)unq | ((int)(qvalid != 0) & (int)!f & (int)tc.qex);
+      any_un = __ballot(in && un) != 0;
+    }
+  } else {
+    any_un = __ballot(in && un) != 0;
+  }
+  if (__builtin_expect(any_un, 0)) {  // the exact sincos of the fired projectiles
     if constexpr (FAST) {  // ... and of the move and the projectile in flight
       const double qa = f ? rn : qrot;
       bool k0, k1;
@@ -1386,7 +1428,9 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
     S.va = (uint32_t)aoff * 8u;
     S.vd = (uint32_t)L.ic;
     S.aso = S.dso = 0;
-    const bool full_wave = __ballot(L.in) == ~0ull;  // wave-uniform
+    S.maybe = 0;
+    const unsigned long long in_mask = __ballot(L.in);
+    const bool full_wave = in_mask == ~0ull;  // wave-uniform
     auto steady_tick = [&](auto full, const float2& cur, float2& nxt) __attribute__((always_inline)) {
       SplitRaw w;
       split_load_pack<POL>(a, rp, L, w);
@@ -1404,7 +1448,8 @@ __global__ void __launch_bounds__(BLK + (PF > 0 ? 64 : 0)) k_step_split_multi(Mu
       SplitPre pre{};
       if constexpr (FAST) {
         pre = split_fast_pre(tc.m, tc.mok, cur, c);
-        split_pre_pin(pre);
+        const unsigned long long unsafe = split_pre_pin(pre);
+        S.maybe = split_pre_maybe(unsafe, tc.qex, decltype(full)::value ? ~0ull : in_mask);
       }
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (kSteadyPrio) {
