@@ -421,6 +421,62 @@ int sk_env_act_step_pool(sk_env* env, const uint64_t* nets, int32_t n_actors, co
                          int32_t random_positions, float* obs_reset, float* ring, int64_t capacity, int64_t* total,
                          uint32_t* arrivals, int64_t* total_copy, void* stream);
 
+/* Scripted actors (ABI 13, added: new symbols, nothing existing changes, so
+ * SK_ABI_VERSION stays 13): four fixed closed-form policies on the game
+ * state, seated wherever a net is.  An action is (move, look) as everywhere
+ * else, and every seat keeps auto-firing (the step does that).  The policy of
+ * player p with opponent o on the pre-tick state, in fp64 without
+ * contraction (csrc/sk_bot.hpp, the one text both backends compile):
+ *   (s, c) = sin, cos of rot[p], the step's own primitive
+ *   dx = x[o] - x[p];  dy = y[o] - y[p]
+ *   side = s dy - c dx;  ahead = -(s dx) - c dy
+ *   ahead > 0: t = side / (ahead look_speed), look = t clamped to [-1, 1]
+ *   else:      look = -1 if side < 0 else 1
+ *   STILL  (0, 0)          RANDOM  sk_gen_random_actions' two floats of this
+ *   AIMER  (0, look)               (game, player) at the current step counter
+ *   CHASER (1 if dx dx + dy dy > (8 player_size)^2 else 0, look)
+ * look_speed and player_size are the env's sk_config's. */
+#define SK_BOT_STILL 1
+#define SK_BOT_RANDOM 2
+#define SK_BOT_AIMER 3
+#define SK_BOT_CHASER 4
+
+/* Both seats' actions of one kind from the env's current state at the current
+ * step counter: actions float[2][N][2] (player-major, as sk_env_step takes
+ * them).  Advances nothing.  Both backends (a HOST pointer on the CPU one);
+ * they give the same floats (for |rot| < 1.6e6, where both take sin and cos
+ * from the same branch-free routine).  SK_EINVAL for a NULL handle or actions, a kind
+ * outside [1, 4] or actions not 8-byte aligned.  Stream-ordered. */
+int sk_env_bot_act(sk_env* env, int32_t kind, float* actions, void* stream);
+
+/* sk_env_act_league, sk_env_act_league_rec and sk_env_act_step_pool with
+ * scripted actors among the seats: every argument, check and result is the
+ * namesake's, with one difference.  A row of nets whose first word is 0 and
+ * whose second word is a kind code in [1, 4] is a scripted actor: its seat
+ * runs no actor forward, each of its (game, player) lanes acts by the policy
+ * above on the state the tick starts from (RANDOM keyed by the env's seed, the
+ * game's global id and the step counter + the ticks the call has run, as the
+ * per-tick loop's sk_env_bot_act calls would be), and a record keeps the
+ * policy's action.  Every other row is a net under the namesake's guard.  In
+ * the pool tick a scripted actor draws no noise even when it is noisy_actor;
+ * *call_counter still advances as the namesake's does.  The three namesakes
+ * keep refusing a null address. */
+int sk_env_act_league_bots(sk_env* env, const uint64_t* nets, int32_t n_actors, const int32_t* pairs,
+                           int32_t n_pairs, int32_t block, float* obs2, float* returns, int32_t* lengths,
+                           int32_t* last_half, int32_t n_ticks, int32_t reward_kind, int32_t tick_limit,
+                           void* stream);
+int sk_env_act_league_bots_rec(sk_env* env, const uint64_t* nets, int32_t n_actors, const int32_t* pairs,
+                               int32_t n_pairs, int32_t block, float* obs2, float* returns, int32_t* lengths,
+                               int32_t* last_half, int32_t n_ticks, int32_t reward_kind, int32_t tick_limit,
+                               const sk_match_record* rec, void* stream);
+int sk_env_act_step_pool_bots(sk_env* env, const uint64_t* nets, int32_t n_actors, const int32_t* pairs,
+                              int32_t n_pairs, int32_t block, int32_t noisy_actor, const float* acting_obs,
+                              float* actions, float noise_sd, float action_sd, uint64_t noise_seed,
+                              uint64_t* call_counter, float* obs, float* reward, int32_t reward_kind, uint8_t* done,
+                              uint8_t* winner, int32_t tick_limit, int32_t auto_reset, int32_t random_positions,
+                              float* obs_reset, float* ring, int64_t capacity, int64_t* total, uint32_t* arrivals,
+                              int64_t* total_copy, void* stream);
+
 /* sk_env_act_step prepared, not launched (ABI 8): the same arguments
  * (N % 4 == 0, ring given or not) into *job, and the env advances its step
  * slot as if the launch had been issued.  The job is then run, exactly once

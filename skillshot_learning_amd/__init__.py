@@ -8,5 +8,7 @@ libskillshot.so (C ABI: include/skillshot.h), bound here with ctypes.
 from ._capi import SkillshotError, load as load_library, lib_path  # noqa: F401
 from .vec_env import FEATURE_KEYS, VecSkillshotGame  # noqa: F401
 from .record import MatchRecord  # noqa: F401
+from .scripted import ScriptedActor  # noqa: F401
 
-__all__ = ["SkillshotError", "VecSkillshotGame", "MatchRecord", "FEATURE_KEYS", "load_library", "lib_path"]
+__all__ = ["SkillshotError", "VecSkillshotGame", "MatchRecord", "ScriptedActor", "FEATURE_KEYS", "load_library",
+           "lib_path"]

@@ -23,6 +23,9 @@
 //   k_act_step_pool32  the opponent-pool training tick: each block of games
 //                    acts from the two actors its pairing names, one of them
 //                    the noisy learner, then steps and inserts as k_act_step32
+//   k_act_league32_bots, k_act_step_pool32_bots  the league (plain and
+//                    recording) and the pool tick where a seat may be a
+//                    scripted actor (csrc/sk_bot.hpp): no tile for that seat
 //   k_split_pack32   the actor's split pack from its flat fp32 parameters
 // and, at the end, their host launchers (sk_launch_act_*, declared in
 // sk_step.hpp and called by sk_engine.hip and sk_learn32.hip) and C entry
@@ -633,11 +636,20 @@ __device__ __forceinline__ void rec_state(const RecArgs& rc, int64_t at, int p, 
 // arguments, k_act_league32 on the two actors its pairing names.  REC (the
 // _rec kernels): the workgroup's games are games rec_k0 .. rec_k0 + 31 of
 // block rec_b of the record `rc`; every line of it is under if constexpr.
-template <bool REC>
+// BOTS (the _bots kernels): seat s + 1 is the scripted actor of kind
+// kind<s + 1> when that is non-zero (workgroup-uniform: it follows from the
+// pairing).  Such a seat runs no tile; wave 0's lanes of that seat compute
+// the policy (sk::bot_lane) on what split_load loaded and the partner lane's
+// position, at step L.step + t (the launch's step value is the same at every
+// tick; the per-tick loop's counter has advanced by t), and store it into
+// sAct where the tile would have, ahead of the barrier wave 0 reads sAct
+// behind.  With both seats scripted waves 1-3 only keep the barriers.  Every
+// line of it is under if constexpr as well.
+template <bool REC, bool BOTS = false>
 __device__ __forceinline__ void match_ticks32(const float* aflat1, const char* apack1, const float* aflat2,
                                               const char* apack2, const sk::StepArgs& a, const sk::Cfg& c,
                                               const MatchArgs& mt, char* smem, const RecArgs* rc = nullptr,
-                                              int rec_b = 0, int rec_k0 = 0) {
+                                              int rec_b = 0, int rec_k0 = 0, int kind1 = 0, int kind2 = 0) {
   float2* sAct = (float2*)(smem + kActorTileLds);
   int* sAlive = (int*)(sAct + 64);
   const int lane = threadIdx.x & 63;
@@ -671,10 +683,25 @@ __device__ __forceinline__ void match_ticks32(const float* aflat1, const char* a
     at.reward = mt.returns;
     sk::StepLane L;
     if (w0) L = sk::split_load(at, gt, slot);  // lanes past the tail: in = false
-    actor_tile32<false>(net_of(af1, kALd, 2), pk1, at.acting_obs, nullptr, RowsSeat{0, g0, n}, 0.f, 0.f, 0, 0,
-                        actor_lds(smem), sAct);
-    actor_tile32<false>(net_of(af2, kALd, 2), pk2, at.acting_obs, nullptr, RowsSeat{n, g0, n}, 0.f, 0.f, 0, 0,
-                        actor_lds(smem), sAct + 32);
+    if constexpr (BOTS) {
+      if (!kind1)
+        actor_tile32<false>(net_of(af1, kALd, 2), pk1, at.acting_obs, nullptr, RowsSeat{0, g0, n}, 0.f, 0.f, 0, 0,
+                            actor_lds(smem), sAct);
+      if (!kind2)
+        actor_tile32<false>(net_of(af2, kALd, 2), pk2, at.acting_obs, nullptr, RowsSeat{n, g0, n}, 0.f, 0.f, 0, 0,
+                            actor_lds(smem), sAct + 32);
+      if (w0 && (kind1 | kind2)) {
+        const int kind = (lane & 1) ? kind2 : kind1;
+        const float2 b = sk::bot_lane(kind, lane & 1, L.pp, L.rot, c, a.seed, (uint64_t)(a.env_offset + L.ic),
+                                      L.step + (uint64_t)t);
+        if (kind) sAct[(lane & 1) * 32 + (lane >> 1)] = b;
+      }
+    } else {
+      actor_tile32<false>(net_of(af1, kALd, 2), pk1, at.acting_obs, nullptr, RowsSeat{0, g0, n}, 0.f, 0.f, 0, 0,
+                          actor_lds(smem), sAct);
+      actor_tile32<false>(net_of(af2, kALd, 2), pk2, at.acting_obs, nullptr, RowsSeat{n, g0, n}, 0.f, 0.f, 0, 0,
+                          actor_lds(smem), sAct + 32);
+    }
     if (w0) {
       // the reference's loop test (:304) on the pre-tick state; both lanes of a game agree
       const bool alive = L.in && ((L.mi.y >> 16) & 0xff) && L.mi.x < a.tick_limit;
@@ -815,6 +842,43 @@ __global__ void __launch_bounds__(kFwdThreads, kEpisodeWaves) k_act_league32_rec
   match_ticks32<true>((const float*)f1, (const char*)k1, (const float*)f2, (const char*)k2, a, c, mt, (char*)smem_sl,
                       &rc, p, ((int)blockIdx.x - p * rc.wgs_per_block) * 32);
 }
+// A league with scripted actors among its seats (sk_env_act_league_bots /
+// _bots_rec): k_act_league32's workgroup, where a row of nets whose first
+// word is 0 and whose second is a kind code in [1, 4] is a scripted actor
+// (include/skillshot.h, csrc/sk_bot.hpp) and every other row a net under the
+// guard above.  A kernel of its own, so that the net-only kernels keep their
+// code; one template for the plain and the recording form (REC false: rc is
+// not read).
+__device__ __forceinline__ int bot_kind(uint64_t flat, uint64_t word) {
+  return (!flat && word >= (uint64_t)SK_BOT_STILL && word <= (uint64_t)SK_BOT_CHASER) ? (int)word : 0;
+}
+__device__ __forceinline__ bool net_ok(uint64_t flat, uint64_t pack) {
+  return flat && pack && !(flat & 3) && !(pack & 15);
+}
+template <bool REC>
+__global__ void __launch_bounds__(kFwdThreads, kEpisodeWaves) k_act_league32_bots(LeagueArgs lg, sk::StepArgs a,
+                                                                                     sk::Cfg c, MatchArgs mt,
+                                                                                     RecArgs rc) {
+  extern __shared__ __attribute__((aligned(16))) float smem_sl[];
+  const int p = (int)blockIdx.x / lg.wgs_per_pair;
+  const int i1 = lg.pairs[2 * p], i2 = lg.pairs[2 * p + 1];
+  uint64_t f1 = 0, k1 = 0, f2 = 0, k2 = 0;
+  if ((unsigned)i1 < (unsigned)lg.n_actors && (unsigned)i2 < (unsigned)lg.n_actors) {
+    f1 = lg.nets[2 * i1];
+    k1 = lg.nets[2 * i1 + 1];
+    f2 = lg.nets[2 * i2];
+    k2 = lg.nets[2 * i2 + 1];
+  }
+  const int b1 = bot_kind(f1, k1), b2 = bot_kind(f2, k2);
+  if (!(b1 || net_ok(f1, k1)) || !(b2 || net_ok(f2, k2))) {
+    const int64_t g = (int64_t)blockIdx.x * 32 + threadIdx.x;
+    if (threadIdx.x < 32 && g < a.n) mt.lengths[g] = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && mt.last_half) *mt.last_half = mt.n_ticks & 1;
+    return;
+  }
+  match_ticks32<REC, true>((const float*)f1, (const char*)k1, (const float*)f2, (const char*)k2, a, c, mt,
+                           (char*)smem_sl, &rc, p, ((int)blockIdx.x - p * lg.wgs_per_pair) * 32, b1, b2);
+}
 
 // The opponent-pool training tick (sk_env_act_step_pool): k_act_step32's tick
 // with k_act_league32's seating.  Workgroup b owns games 32b .. 32b + 31 and
@@ -893,6 +957,76 @@ __global__ void __launch_bounds__(kFwdThreads, kPoolWaves) k_act_step_pool32(Poo
       else
         actor_tile32<false>(net_of(af, kALd, 2), ap, a.acting_obs, act_out, R, 0.f, noisy ? action_sd : 0.f, seed,
                             call, actor_lds(smem), sAct + 32 * seat);
+    }
+  }
+  __syncthreads();
+  if (w0) sk::split_finish(a, c, L, ok ? sAct[(lane & 1) * 32 + (lane >> 1)] : make_float2(0.f, 0.f), slot);
+  if (draws) {
+    __syncthreads();
+    advance_call32(call_ctr, call, gridDim.x);
+  }
+}
+// The pool tick with scripted actors among its seats
+// (sk_env_act_step_pool_bots): k_act_step_pool32 line for line (a kernel of
+// its own, so that the net-only tick keeps its code), where a row of nets
+// that bot_kind reads as a kind is a scripted actor.  Its seat runs no tile:
+// after the seat loop wave 0's lanes of that seat compute the policy on what
+// split_load loaded (sk::bot_lane, at the launch's step value) and store it
+// to sAct and to `act_out`, as the tile would have.  A scripted actor draws
+// no noise even when it is `noisy_actor`; the call number advances as above.
+__global__ void __launch_bounds__(kFwdThreads, kPoolWaves) k_act_step_pool32_bots(
+    PoolArgs pl, float* __restrict__ act_out, float sd, float action_sd, uint64_t seed,
+    uint64_t* __restrict__ call_ctr, sk::StepArgs a, sk::Cfg c) {
+  extern __shared__ __attribute__((aligned(16))) float smem_sl[];
+  char* smem = (char*)smem_sl;
+  float2* sAct = (float2*)(smem + kActorTileLds);
+  const int lane = threadIdx.x & 63;
+  const bool w0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0;
+  const int64_t g0 = (int64_t)blockIdx.x * 32;
+  sk_counters* slot = a.ctr ? a.ctr + (size_t)blockIdx.x * SK_CTR_STRIDE : nullptr;
+  const int p = (int)blockIdx.x / pl.wgs_per_pair;
+  const int i1 = pl.pairs[2 * p], i2 = pl.pairs[2 * p + 1];
+  uint64_t f1 = 0, k1 = 0, f2 = 0, k2 = 0;
+  if ((unsigned)i1 < (unsigned)pl.n_actors && (unsigned)i2 < (unsigned)pl.n_actors) {
+    f1 = pl.nets[2 * i1];
+    k1 = pl.nets[2 * i1 + 1];
+    f2 = pl.nets[2 * i2];
+    k2 = pl.nets[2 * i2 + 1];
+  }
+  const int b1 = bot_kind(f1, k1), b2 = bot_kind(f2, k2);
+  const bool ok = (b1 || net_ok(f1, k1)) && (b2 || net_ok(f2, k2));
+  sk::StepLane L;
+  if (w0) {
+    L = sk::split_load(a, 2 * g0 + lane, slot);
+    if (!ok) L.in = false;
+  }
+  const bool draws = (sd != 0.f || action_sd != 0.f) && call_ctr;
+  const uint64_t call = draws ? call_ctr[0] + 1 : 0;
+  if (ok) {
+#pragma unroll 1
+    for (int seat = 0; seat < 2; ++seat) {
+      if (seat ? b2 : b1) continue;  // workgroup-uniform
+      const float* af = (const float*)(seat ? f2 : f1);
+      const char* ap = (const char*)(seat ? k2 : k1);
+      const bool noisy = (seat ? i2 : i1) == pl.noisy_actor;
+      RowsSeatStore R;
+      R.base = seat ? a.n : 0;
+      R.g0 = g0;
+      R.n = a.n;
+      if (noisy && sd != 0.f)
+        actor_tile32<true>(net_of(af, kALd, 2), ap, a.acting_obs, act_out, R, sd, action_sd, seed, call,
+                           actor_lds(smem), sAct + 32 * seat);
+      else
+        actor_tile32<false>(net_of(af, kALd, 2), ap, a.acting_obs, act_out, R, 0.f, noisy ? action_sd : 0.f, seed,
+                            call, actor_lds(smem), sAct + 32 * seat);
+    }
+    if (w0 && (b1 | b2)) {
+      const int kind = (lane & 1) ? b2 : b1;
+      const float2 b = sk::bot_lane(kind, lane & 1, L.pp, L.rot, c, a.seed, (uint64_t)(a.env_offset + L.ic), L.step);
+      if (kind) {
+        sAct[(lane & 1) * 32 + (lane >> 1)] = b;
+        if (L.in) *(float2*)(act_out + ((int64_t)(lane & 1) * a.n + L.i) * 2) = b;
+      }
     }
   }
   __syncthreads();
@@ -1211,6 +1345,44 @@ int sk_launch_act_step_pool32(const uint64_t* nets, int n_actors, const int32_t*
   const unsigned G = (unsigned)(a.n / 32);
   const PoolArgs pl{nets, pairs, n_actors, block / 32, noisy_actor};
   k_act_step_pool32<<<G, kFwdThreads, kActPoolLds, st>>>(pl, act_out, sd, action_sd, seed, call_ctr, a, c);
+  return hipGetLastError() == hipSuccess ? SK_OK : SK_EHIP;
+}
+
+// the same two launches where rows of nets may name scripted actors (sk_env_act_league_bots / _bots_rec,
+// sk_env_act_step_pool_bots): the _bots kernels, every check the net-only launchers make
+int sk_launch_act_league32_bots(const uint64_t* nets, int n_actors, const int32_t* pairs, int block,
+                                const sk::StepArgs& a, const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths,
+                                int32_t* last_half, int n_ticks, const sk_match_record* rec, hipStream_t st) {
+  static bool attr = false;
+  if (!attr) {
+    set_lds32(k_act_league32_bots<false>, kActMatchLds);
+    set_lds32(k_act_league32_bots<true>, kActMatchLds);
+    attr = true;
+  }
+  if (!seating_ok(nets, n_actors, pairs, block, a) || !rec_ok(rec, a.n / block, block)) return SK_EINVAL;
+  const unsigned G = (unsigned)(a.n / 32);
+  const MatchArgs mt{obs2, returns, lengths, last_half, n_ticks};
+  const LeagueArgs lg{nets, pairs, n_actors, block / 32};
+  if (rec)
+    k_act_league32_bots<true><<<G, kFwdThreads, kActMatchLds, st>>>(lg, a, c, mt, rec_args(*rec, block / 32));
+  else
+    k_act_league32_bots<false><<<G, kFwdThreads, kActMatchLds, st>>>(lg, a, c, mt, RecArgs{});
+  return match_finish(a, lengths, st);
+}
+
+int sk_launch_act_step_pool32_bots(const uint64_t* nets, int n_actors, const int32_t* pairs, int block,
+                                   int noisy_actor, float* act_out, float sd, float action_sd, uint64_t seed,
+                                   uint64_t* call_ctr, const sk::StepArgs& a, const sk::Cfg& c, hipStream_t st) {
+  static bool attr = false;
+  if (!attr) {
+    set_lds32(k_act_step_pool32_bots, kActPoolLds);
+    attr = true;
+  }
+  if (!seating_ok(nets, n_actors, pairs, block, a) || !act_out) return SK_EINVAL;
+  if (noisy_actor < -1 || noisy_actor >= n_actors) return SK_EINVAL;
+  const unsigned G = (unsigned)(a.n / 32);
+  const PoolArgs pl{nets, pairs, n_actors, block / 32, noisy_actor};
+  k_act_step_pool32_bots<<<G, kFwdThreads, kActPoolLds, st>>>(pl, act_out, sd, action_sd, seed, call_ctr, a, c);
   return hipGetLastError() == hipSuccess ? SK_OK : SK_EHIP;
 }
 

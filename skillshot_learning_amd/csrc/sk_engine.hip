@@ -16,7 +16,8 @@
 //   translation unit
 //   k_rollout_random      n ticks of the random policy in one launch, state
 //                         held in registers, in-kernel Philox actions
-// Around them: k_gen_actions (random-policy actions into HBM), k_reset /
+// Around them: k_gen_actions (random-policy actions into HBM), k_bot_act (a
+// scripted actor's actions on the current state, sk_bot.hpp), k_reset /
 // k_move_* / k_shoot / k_game_tick / k_observe / k_features (the reference's
 // per-method API, batched), and the host side of the C ABI, which chooses
 // among the kernels above.  For the multi-tick step that choice is a pure
@@ -413,6 +414,22 @@ __global__ void __launch_bounds__(kBlock) k_gen_actions(float4* out, int64_t n, 
     o[(int64_t)t * 2 * n + i] = make_float2(u32_to_action(u.x), u32_to_action(u.y));
     o[(int64_t)t * 2 * n + n + i] = make_float2(u32_to_action(u.z), u32_to_action(u.w));
   }
+}
+
+// sk_env_bot_act: both seats' scripted actions of one kind, lanes (2i, 2i + 1)
+// of a wave owning players 1 and 2 of game i as in k_step_split (bot_lane
+// reads the opponent through the pair exchange).  A lane past the end reads
+// game 0 and stores nothing.
+__global__ void __launch_bounds__(kStepBlock) k_bot_act(View v, int64_t n, int kind, float2* actions, Cfg c,
+                                                        uint64_t seed, int64_t env_offset, StepRef sref) {
+  const int64_t gt = (int64_t)blockIdx.x * kStepBlock + threadIdx.x, i = gt >> 1;
+  const int p = (int)(gt & 1);
+  const bool in = i < n;
+  const int64_t hc = 2 * (in ? i : 0) + p;
+  const int2 pp = reinterpret_cast<const int2*>(v.pos)[hc];
+  const double rot = reinterpret_cast<const double*>(v.rot)[hc];
+  const float2 a = bot_lane(kind, p, pp, rot, c, seed, (uint64_t)(env_offset + i), step_read(sref));
+  if (in) actions[(int64_t)p * n + i] = a;
 }
 
 __global__ void __launch_bounds__(kBlock) k_reset(View v, int64_t n, const uint8_t* mask, int random,
@@ -1277,7 +1294,7 @@ int sk_env_act_match_rec(sk_env* e, const float* actor1_flat, const void* actor1
 static int act_league(sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
                       int32_t block, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
                       int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, bool recording,
-                      const sk_match_record* rec, void* stream) {
+                      const sk_match_record* rec, void* stream, bool bots = false) {
   SK_CHECK_ENV(e);
   StepArgs a;
   int rc = seating_check(e, nets, n_actors, pairs, n_pairs, block);
@@ -1286,8 +1303,9 @@ static int act_league(sk_env* e, const uint64_t* nets, int32_t n_actors, const i
   if (rc == SK_OK && recording) rc = rec_check(rec, n_pairs, block, n_ticks, returns);
   if (rc != SK_OK) return rc;
   if (e->host) return fail(SK_EINVAL, "sk_env_act_league(_rec) runs on the GPU backend");
-  rc = sk_launch_act_league32(nets, n_actors, pairs, block, a, e->dcfg, obs2, returns, lengths, last_half, n_ticks,
-                              rec, (hipStream_t)stream);
+  rc = (bots ? sk_launch_act_league32_bots : sk_launch_act_league32)(nets, n_actors, pairs, block, a, e->dcfg, obs2,
+                                                                     returns, lengths, last_half, n_ticks, rec,
+                                                                     (hipStream_t)stream);
   if (rc != SK_OK) return fail(rc, "k_act_league32(_rec) launch failed");
   e->parity ^= 1;
   return SK_OK;
@@ -1308,12 +1326,29 @@ int sk_env_act_league_rec(sk_env* e, const uint64_t* nets, int32_t n_actors, con
                     tick_limit, true, rec, stream);
 }
 
-int sk_env_act_step_pool(sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
+// sk_env_act_league_bots / _bots_rec: the same checks, the _bots kernels
+int sk_env_act_league_bots(sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
+                           int32_t block, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
+                           int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, void* stream) {
+  return act_league(e, nets, n_actors, pairs, n_pairs, block, obs2, returns, lengths, last_half, n_ticks, reward_kind,
+                    tick_limit, false, nullptr, stream, true);
+}
+
+int sk_env_act_league_bots_rec(sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs,
+                               int32_t n_pairs, int32_t block, float* obs2, float* returns, int32_t* lengths,
+                               int32_t* last_half, int32_t n_ticks, int32_t reward_kind, int32_t tick_limit,
+                               const sk_match_record* rec, void* stream) {
+  return act_league(e, nets, n_actors, pairs, n_pairs, block, obs2, returns, lengths, last_half, n_ticks, reward_kind,
+                    tick_limit, true, rec, stream, true);
+}
+
+// sk_env_act_step_pool and sk_env_act_step_pool_bots
+static int act_step_pool(sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
                          int32_t block, int32_t noisy_actor, const float* acting_obs, float* actions, float noise_sd,
                          float action_sd, uint64_t noise_seed, uint64_t* call_counter, float* obs, float* reward,
                          int32_t reward_kind, uint8_t* done, uint8_t* winner, int32_t tick_limit, int32_t auto_reset,
                          int32_t random_positions, float* obs_reset, float* ring, int64_t capacity, int64_t* total,
-                         uint32_t* arrivals, int64_t* total_copy, void* stream) {
+                         uint32_t* arrivals, int64_t* total_copy, void* stream, bool bots) {
   SK_CHECK_ENV(e);
   int rc = seating_check(e, nets, n_actors, pairs, n_pairs, block);
   if (rc != SK_OK) return rc;
@@ -1327,11 +1362,35 @@ int sk_env_act_step_pool(sk_env* e, const uint64_t* nets, int32_t n_actors, cons
                      random_positions, obs_reset, ring, capacity, total, arrivals, total_copy, a);
   if (rc != SK_OK) return rc;
   if (e->host) return fail(SK_EINVAL, "sk_env_act_step_pool runs on the GPU backend");
-  rc = sk_launch_act_step_pool32(nets, n_actors, pairs, block, noisy_actor, actions, noise_sd, action_sd, noise_seed,
-                                 call_counter, a, e->dcfg, (hipStream_t)stream);
+  rc = (bots ? sk_launch_act_step_pool32_bots : sk_launch_act_step_pool32)(
+      nets, n_actors, pairs, block, noisy_actor, actions, noise_sd, action_sd, noise_seed, call_counter, a, e->dcfg,
+      (hipStream_t)stream);
   if (rc != SK_OK) return fail(rc, "k_act_step_pool32 launch failed");
   e->parity ^= 1;
   return SK_OK;
+}
+
+int sk_env_act_step_pool(sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
+                         int32_t block, int32_t noisy_actor, const float* acting_obs, float* actions, float noise_sd,
+                         float action_sd, uint64_t noise_seed, uint64_t* call_counter, float* obs, float* reward,
+                         int32_t reward_kind, uint8_t* done, uint8_t* winner, int32_t tick_limit, int32_t auto_reset,
+                         int32_t random_positions, float* obs_reset, float* ring, int64_t capacity, int64_t* total,
+                         uint32_t* arrivals, int64_t* total_copy, void* stream) {
+  return act_step_pool(e, nets, n_actors, pairs, n_pairs, block, noisy_actor, acting_obs, actions, noise_sd, action_sd,
+                       noise_seed, call_counter, obs, reward, reward_kind, done, winner, tick_limit, auto_reset,
+                       random_positions, obs_reset, ring, capacity, total, arrivals, total_copy, stream, false);
+}
+
+int sk_env_act_step_pool_bots(sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs,
+                              int32_t n_pairs, int32_t block, int32_t noisy_actor, const float* acting_obs,
+                              float* actions, float noise_sd, float action_sd, uint64_t noise_seed,
+                              uint64_t* call_counter, float* obs, float* reward, int32_t reward_kind, uint8_t* done,
+                              uint8_t* winner, int32_t tick_limit, int32_t auto_reset, int32_t random_positions,
+                              float* obs_reset, float* ring, int64_t capacity, int64_t* total, uint32_t* arrivals,
+                              int64_t* total_copy, void* stream) {
+  return act_step_pool(e, nets, n_actors, pairs, n_pairs, block, noisy_actor, acting_obs, actions, noise_sd, action_sd,
+                       noise_seed, call_counter, obs, reward, reward_kind, done, winner, tick_limit, auto_reset,
+                       random_positions, obs_reset, ring, capacity, total, arrivals, total_copy, stream, true);
 }
 
 static_assert(sizeof(ActStepJob) <= sizeof(sk_step_job), "sk_step_job too small for ActStepJob");
@@ -1565,6 +1624,21 @@ int sk_gen_random_actions(sk_env* e, float* actions, int32_t n_ticks, void* stre
   if (e->host) return skh::gen_random_actions(*e->host, actions, n_ticks), SK_OK;
   k_gen_actions<<<grid_for(e->n), kBlock, 0, (hipStream_t)stream>>>(
       reinterpret_cast<float4*>(actions), e->n, n_ticks, e->seed, e->env_offset, StepRef{e->d_step, e->parity});
+  SK_LAUNCH_CHECK();
+  return SK_OK;
+}
+
+// both seats' scripted actions of one kind (csrc/sk_bot.hpp) from the current state at the current step value:
+// k_bot_act, two lanes per game like k_step_split; advances nothing
+int sk_env_bot_act(sk_env* e, int32_t kind, float* actions, void* stream) {
+  SK_CHECK_ENV(e);
+  if (!actions) return fail(SK_EINVAL, "actions is NULL");
+  if (!skbot::kind_ok(kind)) return fail(SK_EINVAL, "kind must be one of SK_BOT_STILL .. SK_BOT_CHASER");
+  if (((uintptr_t)actions) & 7) return fail(SK_EINVAL, "actions must be 8-byte aligned");
+  if (e->host) return skh::bot_act(*e->host, kind, actions), SK_OK;
+  k_bot_act<<<step_grid(2 * (int64_t)e->n), kStepBlock, 0, (hipStream_t)stream>>>(
+      e->view, e->n, kind, reinterpret_cast<float2*>(actions), e->dcfg, e->seed, e->env_offset,
+      StepRef{e->d_step, e->parity});
   SK_LAUNCH_CHECK();
   return SK_OK;
 }

@@ -25,7 +25,10 @@
 #include <thread>
 #include <vector>
 
+#include <hip/hip_runtime.h>  // hipcc compiles this file as HIP: sk_bot.hpp / sk_trig.hpp then want its qualifiers
+
 #include "../../include/skillshot.h"
+#include "sk_bot.hpp"
 #include "sk_host.hpp"
 
 namespace skh {
@@ -543,6 +546,32 @@ void gen_random_actions(Host& h, float* actions, int n_ticks) {
         o[2 * i + 1] = u32_to_action(u.y);
         o[2 * (n + i)] = u32_to_action(u.z);
         o[2 * (n + i) + 1] = u32_to_action(u.w);
+      }
+    }
+  });
+}
+
+// sk_env_bot_act: the scripted policy (sk_bot.hpp, the text the device
+// compiles) of both players of every game on the current state, the random
+// policy's draw gen_random_actions' at the current step
+void bot_act(Host& h, int kind, float* actions) {
+  const int64_t n = h.n;
+  const auto lib = [](double x) { return sktrig::SinCos{std::sin(x), std::cos(x)}; };
+  for_envs(h, [&](int64_t lo, int64_t hi, sk_counters&) {
+    for (int64_t i = lo; i < hi; ++i) {
+      Env e;
+      load(h, i, e);
+      float r[4] = {0.f, 0.f, 0.f, 0.f};
+      if (kind == SK_BOT_RANDOM) {
+        const U4 u = draw4(h.seed, (uint64_t)(h.env_offset + i), h.step, 0u);
+        r[0] = u32_to_action(u.x); r[1] = u32_to_action(u.y); r[2] = u32_to_action(u.z); r[3] = u32_to_action(u.w);
+      }
+      for (int p = 0; p < 2; ++p) {
+        const int o = 1 - p;
+        const skbot::Act a = skbot::policy(kind, skbot::sincos(e.rot[p], lib), e.px[o] - e.px[p], e.py[o] - e.py[p],
+                                           h.cfg.look_speed, h.cfg.player_size, r[2 * p], r[2 * p + 1]);
+        actions[2 * ((int64_t)p * n + i)] = a.move;
+        actions[2 * ((int64_t)p * n + i) + 1] = a.look;
       }
     }
   });

@@ -42,6 +42,8 @@ void observe(Host& h, float* obs, float* reward, int kind);
 void step(Host& h, const float* actions, float* obs, float* reward, int kind, uint8_t* done, uint8_t* winner,
           int tick_limit, int auto_reset, int random_positions, float* obs_reset);
 void gen_random_actions(Host& h, float* actions, int n_ticks);
+// sk_env_bot_act on host planes: actions float[2][N][2]
+void bot_act(Host& h, int kind, float* actions);
 void rollout_random(Host& h, int n_ticks, int tick_limit);
 // sk_render_states on host planes (validated by the caller): out uint8[m][W][H]
 void render(const sk_config& cfg, const sk_state_view& v, const int64_t* ids, int64_t m, uint8_t* out);

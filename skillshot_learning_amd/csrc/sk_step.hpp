@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sk_bot.hpp"
 #include "sk_device.hpp"
 
 // Step kernels (k_step*, k_rollout_random) launch one-wave workgroups: 64 vs
@@ -496,6 +497,30 @@ __device__ __forceinline__ void split_finish(const StepArgs& a, const Cfg& c, co
   }
 }
 
+// ------------------------------------------------------------------ scripted actors
+// The action a scripted actor of kind `kind` (SK_BOT_*, csrc/sk_bot.hpp; 0:
+// none, the lane gets zeros) takes in this (game, player) lane on the state
+// the tick starts from: the lane's own position and rotation (split_load's pp
+// and rot), the partner lane's position through the pair exchange, the env's
+// look speed and player size, and for the random policy sk_gen_random_actions'
+// draw of global game `genv` at step `step`.  Every lane of the wave calls it
+// (the exchange reads the partner); `kind` may differ between the two lanes
+// of a game.
+__device__ __forceinline__ float2 bot_lane(int kind, int p, int2 pp, double rot, const Cfg& c, uint64_t seed,
+                                           uint64_t genv, uint64_t step) {
+  const int ox = pair_swap(pp.x), oy = pair_swap(pp.y);
+  if (!kind) return make_float2(0.f, 0.f);
+  float r0 = 0.f, r1 = 0.f;
+  if (kind == SK_BOT_RANDOM) {
+    const U4 u = draw4(seed, genv, step, 0u);
+    r0 = u32_to_action(p ? u.z : u.x);
+    r1 = u32_to_action(p ? u.w : u.y);
+  }
+  const sktrig::SinCos m = skbot::sincos(rot, [](double x) { return sincos_lib(x); });
+  const skbot::Act a = skbot::policy(kind, m, ox - pp.x, oy - pp.y, c.look, c.psize, r0, r1);
+  return make_float2(a.move, a.look);
+}
+
 }  // namespace sk
 
 // k_act_step32 (csrc/sk_act32.hpp): the fp32 actor forward and k_step_split
@@ -519,3 +544,10 @@ int sk_launch_act_league32(const uint64_t* nets, int n_actors, const int32_t* pa
 int sk_launch_act_step_pool32(const uint64_t* nets, int n_actors, const int32_t* pairs, int block, int noisy_actor,
                               float* act_out, float sd, float action_sd, uint64_t seed, uint64_t* call_ctr,
                               const sk::StepArgs& a, const sk::Cfg& c, hipStream_t st);
+// k_act_league32_bots / k_act_step_pool32_bots (csrc/sk_act32.hpp): the two above with scripted actors among the seats
+int sk_launch_act_league32_bots(const uint64_t* nets, int n_actors, const int32_t* pairs, int block,
+                                const sk::StepArgs& a, const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths,
+                                int32_t* last_half, int n_ticks, const sk_match_record* rec, hipStream_t st);
+int sk_launch_act_step_pool32_bots(const uint64_t* nets, int n_actors, const int32_t* pairs, int block,
+                                   int noisy_actor, float* act_out, float sd, float action_sd, uint64_t seed,
+                                   uint64_t* call_ctr, const sk::StepArgs& a, const sk::Cfg& c, hipStream_t st);

@@ -37,6 +37,7 @@ import torch.nn.functional as F
 
 from ._capi import SkillshotError
 from .rng import DROP_SCALE, dropout_keep
+from .scripted import ScriptedActor, as_scripted
 
 STATE_DIM = 12   # SkillshotLearner.py:54
 ACTION_DIM = 2   # :55
@@ -1162,7 +1163,10 @@ class SkillshotLearner:
                   baseline), an Actor module, an actor state_dict, another
                   SkillshotLearner, or an int checkpoint index under
                   save_location (load_actor_critic_models' load_index; only
-                  the actor is read, into a net of its own)
+                  the actor is read, into a net of its own), or a scripted
+                  actor: a ScriptedActor or one of "still", "random",
+                  "aimer", "chaser" (scripted.py: a fixed yardstick that
+                  acts on the env's state, not on observations)
         games     games per leg (default n_envs); tick_limit (default the
                   learner's) ends a game as a draw
         swap_sides  play two legs from IDENTICAL start states, the learner in
@@ -1189,6 +1193,9 @@ class SkillshotLearner:
         games masked as model_train's loop masks them) on either backend.
         Outcomes are read off the final states once, at the end
         (match_outcomes: winner_id is the id of the player who was HIT).
+        Against a scripted opponent a leg on the kernel path is a league
+        launch of one pairing (act_league: the scripted seat runs no tile);
+        the loop path asks bot_actions for that seat instead of a forward.
 
         Returns dict(games, wins, losses, draws, win_rate, loss_rate,
         draw_rate, mean_ticks, mean_return, opponent_mean_return, legs=[the
@@ -1234,7 +1241,8 @@ class SkillshotLearner:
         play with i in seat 1 against j).
 
         actors  a sequence of 2 to 32 entries of the kinds evaluate takes as
-                `opponent`; None is the learner's current actor.  The nets
+                `opponent`, scripted actors included (an absolute anchor:
+                "Elo above chaser"); None is the learner's current actor.  The nets
                 built for them are held until the next league call (a holder
                 of league's own, not evaluate's 8-entry cache).
         games   games per ordered pairing (default n_envs)
@@ -1251,7 +1259,10 @@ class SkillshotLearner:
         reset: each block holds the `games` start states, then pad games that
         are not live.  The tallies are reduced on the device and read once.
         Otherwise, or with SK_LEAGUE_KERNEL=0, the pairings play one by one
-        with evaluate's leg.  Nothing of training moves (evaluate's promise).
+        with evaluate's leg (a pairing that seats the scripted random policy
+        on a twin env whose games carry the ids they have in the one launch,
+        the key of its draws).  Nothing of training moves (evaluate's
+        promise).
 
         Returns a dict.  Ordered tables, nested lists [K][K], row = seat 1,
         column = seat 2, diagonal 0: seat_wins (player 2 was hit), seat_losses
@@ -1290,10 +1301,16 @@ class SkillshotLearner:
         else:
             start = g.state_dict()
             legs, recs = [], []
+            block = 32 * ((n + 31) // 32)
             for k, (i, j) in enumerate(pairs):
+                # a scripted random seat draws by the game's global id: pairing k's games carry the ids they
+                # have in the one launch, k blocks on
+                keyed = k and any(isinstance(players[q][0], ScriptedActor) and players[q][0].name == "random"
+                                  for q in (i, j))
+                gk = self._eval_env(n, limit, seed, shift=k * block) if keyed else g
                 if k:
-                    g.load_state_dict(start)
-                legs.append(self._match_leg(g, players[i], players[j], 1, limit, reward,
+                    gk.load_state_dict(start)
+                legs.append(self._match_leg(gk, players[i], players[j], 1, limit, reward,
                                             self._match_kernel_usable() and players[i][1] is not None and
                                             players[j][1] is not None and
                                             os.environ.get("SK_MATCH_KERNEL", "1") != "0", record=r, records=recs))
@@ -1334,7 +1351,7 @@ class SkillshotLearner:
         from .vec_env import PLANES, VecSkillshotGame
         P, block = len(pairs), 32 * ((games + 31) // 32)
         envs = self.__dict__.setdefault("_league_envs", {})
-        key = (P, block, limit, g.seed)
+        key = (P, block, limit, g.seed) + ((g.env_offset,) if g.env_offset != self.game_environment.env_offset else ())
         lg = envs.get(key)
         if lg is None:
             lg = envs[key] = VecSkillshotGame(P * block, device=self.device, seed=g.seed, env_offset=g.env_offset,
@@ -1342,7 +1359,7 @@ class SkillshotLearner:
             lg._league_obs = torch.zeros((2, P, block, 12), dtype=torch.float32, device=self.device)
         if getattr(lg, "_league_ret", None) is None or lg._league_ret.shape[1] != games:
             lg._league_ret = torch.empty((2, games), dtype=torch.float32, device=self.device)
-        lg.step_counter = 0
+        lg.step_counter = g.step_counter  # the key of a scripted random seat's draws, as the pair-by-pair path has it
         for name, _, w in PLANES:  # every block: the start states, then pad games (game 0's state, not live)
             src, dst = getattr(g, name), getattr(lg, name).view(P, block, w)
             dst[:, :games] = src[None]
@@ -1370,14 +1387,17 @@ class SkillshotLearner:
         rec.games = rec.games % block
         return tallies, rec
 
-    def _eval_env(self, games, tick_limit, seed):
+    def _eval_env(self, games, tick_limit, seed, shift=0):
+        """the evaluation env of (games, tick_limit, seed); shift > 0: its twin
+        whose games carry the global ids `shift` further on (league's
+        pair-by-pair path: the ids a pairing's games have in the one launch)"""
         from .vec_env import VecSkillshotGame
         tr = self.game_environment
         s = int((tr.seed * 1000003 + 0x5EED) & ((1 << 63) - 1) if seed is None else seed)
         envs = self.__dict__.setdefault("_eval_envs", {})
-        key = (games, tick_limit, s)
+        key = (games, tick_limit, s) + ((shift,) if shift else ())
         if key not in envs:
-            envs[key] = VecSkillshotGame(games, device=self.device, seed=s, env_offset=tr.env_offset,
+            envs[key] = VecSkillshotGame(games, device=self.device, seed=s, env_offset=tr.env_offset + shift,
                                          tick_limit=tick_limit, random_positions=self.use_random_start)
         return envs[key]
 
@@ -1394,6 +1414,14 @@ class SkillshotLearner:
         losses, draws, the games' ticks, the own and the other seat's reward
         sums (fp32 sums over the games).  record > 0: the MatchRecord of the
         leg's first `record` games is appended to `records`."""
+        if use_kernel and (isinstance(a1[1], ScriptedActor) or isinstance(a2[1], ScriptedActor)):
+            # a scripted seat: the leg as a league of one pairing (act_match seats two nets)
+            row = self._league_launch(g, [a1[1], a2[1]], [(0, 1)], g.n, limit, reward, record=record)
+            if record:
+                row, rec = row
+                rec.pairs = None
+                records.append(rec)
+            return row[0] if seat == 1 else row[0][[1, 0, 2, 3, 5, 4]]
         obs, _ = g.observe(reward=reward)
         if use_kernel:
             m = g.act_match(a1[1], a2[1], obs, n_ticks=limit, reward=reward,
@@ -1432,6 +1460,9 @@ class SkillshotLearner:
 
         if opponent is None:
             return pair(self.model_actor, self.actor_kernel)
+        bot = as_scripted(opponent)
+        if bot is not None:  # a scripted actor stands in both places: the loop paths and the kernels ask it
+            return bot, bot
         if isinstance(opponent, SkillshotLearner):
             if opponent.device == self.device and type(opponent.actor_kernel) is type(self.actor_kernel):
                 return pair(opponent.model_actor, opponent.actor_kernel)
@@ -1440,7 +1471,8 @@ class SkillshotLearner:
         if bounded:
             cache = self.__dict__.setdefault("_eval_opponents", {})
         if isinstance(opponent, bool) or not isinstance(opponent, (int, np.integer, dict, nn.Module)):
-            raise TypeError("opponent: None, an Actor, an actor state_dict, a SkillshotLearner or a checkpoint index")
+            raise TypeError("opponent: None, an Actor, an actor state_dict, a SkillshotLearner, a checkpoint index, "
+                            "a ScriptedActor or its name")
         if isinstance(opponent, (int, np.integer)):
             key = ("checkpoint", int(opponent))
         else:
@@ -1488,8 +1520,13 @@ class SkillshotLearner:
         ticks, winner = g.ticks.clone(), g.winner_id.clone()
         played = torch.zeros(n, dtype=torch.int32, device=dev)
         t = 0
+        scripted = isinstance(act1, ScriptedActor) or isinstance(act2, ScriptedActor)
         while bool(alive.any()):
-            act = torch.stack((act1(obs[0]), act2(obs[1])))
+            if scripted:  # a scripted seat acts on the env's state, not on obs
+                act = torch.stack([a.actions(g)[p] if isinstance(a, ScriptedActor) else a(obs[p]).float()
+                                   for p, a in enumerate((act1, act2))])
+            else:
+                act = torch.stack((act1(obs[0]), act2(obs[1])))
             if record is not None:
                 ar = record.loop_before(g, t, alive)
             out = g.step(act, obs=True, reward=reward, auto_reset=False)
@@ -1568,8 +1605,9 @@ class SkillshotLearner:
 
         opponents  a list of what evaluate takes as `opponent`: an Actor, an
                    actor state_dict, another SkillshotLearner, a checkpoint
-                   index, or None (the learner's current actor, without
-                   noise).  Their weights are read at the call, into nets of
+                   index, a scripted actor (a ScriptedActor or its name:
+                   a curriculum before any checkpoint exists), or None (the
+                   learner's current actor, without noise).  Their weights are read at the call, into nets of
                    train_vs's own (held until the next call); they are never
                    written.
         The games are seated by pool_pairs(n_envs, len(opponents), self_play)
@@ -1624,7 +1662,8 @@ class SkillshotLearner:
                     act = self.model_act(obs)
                     x = obs.reshape(-1, STATE_DIM)
                     for k, (fwd, _) in enumerate(players):
-                        a = fwd(x).reshape(2, -1, ACTION_DIM)
+                        a = (fwd.actions(g) if isinstance(fwd, ScriptedActor) else
+                             fwd(x).reshape(2, -1, ACTION_DIM))
                         act = torch.where((seat == k + 1)[:, :, None], a, act)
                     act = act.contiguous()
                 out = self.do_actions(act, reset_obs=True)

@@ -14,6 +14,7 @@ import torch
 
 from . import _capi
 from ._capi import SkillshotError, check
+from .scripted import ScriptedActor, kind_code
 
 PLANES = (("pos", torch.int32, 4), ("rot", torch.float64, 2), ("qpos", torch.int32, 4),
           ("qrot", torch.float64, 2), ("qcdage", torch.int32, 4), ("misc", torch.int32, 2))
@@ -501,8 +502,9 @@ class VecSkillshotGame:
             raise ValueError("pairs must be a list of (seat-1 actor, seat-2 actor) index pairs")
         if not actors or not plist:
             raise ValueError(f"{what} needs at least one actor and one pairing")
-        if not all(hasattr(a, "flat") and hasattr(a, "ensure_pack") for a in actors):
-            raise TypeError("actors must be ActorKernel32 objects (the fp32 actor with its split pack)")
+        if not all(isinstance(a, ScriptedActor) or (hasattr(a, "flat") and hasattr(a, "ensure_pack")) for a in actors):
+            raise TypeError("actors must be ActorKernel32 objects (the fp32 actor with its split pack) or "
+                            "ScriptedActors")
         if block <= 0 or block % 32:
             raise ValueError("block must be a positive multiple of 32")
         if len(plist) * block != self.n:
@@ -516,8 +518,10 @@ class VecSkillshotGame:
         """the two device tables of a seating (the actors' addresses, the
         pairs), taken from the dict `o` of an earlier call and uploaded only
         when the actors' buffers or the pairs differ from that call's:
-        (nets, pairs, the key to keep as `tables`)"""
-        addr = tuple((a.flat.data_ptr(), a.ensure_pack().data_ptr()) for a in actors)
+        (nets, pairs, the key to keep as `tables`).  A ScriptedActor's row is
+        (0, its kind code): the _bots symbols read it as a scripted seat."""
+        addr = tuple((0, a.kind) if isinstance(a, ScriptedActor) else (a.flat.data_ptr(), a.ensure_pack().data_ptr())
+                     for a in actors)
         nets = self._out_buf(o, "nets", (len(actors), 2), torch.int64)
         prs = self._out_buf(o, "pairs", (len(plist), 2), torch.int32)
         if o.get("tables") != (addr, plist) or nets is not o.get("nets") or prs is not o.get("pairs"):
@@ -642,14 +646,20 @@ class VecSkillshotGame:
         and uploads nothing.  record: act_match's, per pairing — an int r
         records the first r games of every block (row p r + k = game k of
         pairing p; the record's `pairs` names each row's pairing); a pairing
-        the kernel's guard refuses and the pad games record nothing."""
+        the kernel's guard refuses and the pad games record nothing.
+        `actors` may hold ScriptedActors (scripted.py): their seats run no
+        forward, the launch (sk_env_act_league_bots) computes the policy on
+        each tick's state itself and a record keeps the policy's actions; a
+        list of nets alone goes through sk_env_act_league as before."""
         if self.is_cpu:
             raise SkillshotError("act_league runs on the GPU backend (SkillshotLearner.league loops on the CPU one)")
         o = out or {}
         actors, plist, block = self._seating("act_league", actors, pairs, block, o)
         nets, prs, tables = self._seating_tables(actors, plist, o)
         seats = (_ptr(nets), len(actors), _ptr(prs), len(plist), block)
-        res = self._match_launch("act_league", self._L.sk_env_act_league, self._L.sk_env_act_league_rec, seats,
+        bots = any(isinstance(a, ScriptedActor) for a in actors)
+        res = self._match_launch("act_league", self._L.sk_env_act_league_bots if bots else self._L.sk_env_act_league,
+                                 self._L.sk_env_act_league_bots_rec if bots else self._L.sk_env_act_league_rec, seats,
                                  len(plist), block, start_obs, n_ticks, reward, o, resume, record)
         res.update(nets=nets, pairs=prs, tables=tables)
         if "record" in res:
@@ -675,7 +685,11 @@ class VecSkillshotGame:
         uploaded again only when the actors' buffers or `pairs` differ from
         the call that made them (out=); a per-tick caller passes the checked
         pairs back as well (pairs=out["tables"][1]) and skips the host's walk
-        over them.  Returns act_step's dict."""
+        over them.  `actors` may hold ScriptedActors (scripted.py; never
+        the noisy one): their seats act by the policy on the tick's state,
+        in the same launch (sk_env_act_step_pool_bots), equal to
+        bot_actions' rows in the composition above.  Returns act_step's
+        dict."""
         if self.is_cpu:
             raise SkillshotError("act_step_pool runs on the GPU backend (SkillshotLearner.train_vs loops on the CPU one)")
         o = out or {}
@@ -684,10 +698,13 @@ class VecSkillshotGame:
             raise ValueError(f"noisy must be None or an actor index in [0, {len(actors)})")
         if noisy is None and (noise_sd != 0.0 or action_sd != 0.0):
             raise ValueError("noise_sd / action_sd need the noisy actor's index")
+        if noisy is not None and isinstance(actors[int(noisy)], ScriptedActor):
+            raise ValueError("the noisy actor must be a net, not a ScriptedActor")
+        bots = any(isinstance(a, ScriptedActor) for a in actors)
         nets, prs, tables = self._seating_tables(actors, plist, o)
         res, s, ring_args = self._act_step_out(o, acting_obs, actions, reset_obs, ring, total_copy)
         learner = actors[int(noisy)] if noisy is not None else None
-        check(self._L.sk_env_act_step_pool(
+        check((self._L.sk_env_act_step_pool_bots if bots else self._L.sk_env_act_step_pool)(
             self._h, _ptr(nets), len(actors), _ptr(prs), len(plist), block, -1 if noisy is None else int(noisy),
             _ptr(s), _ptr(res["actions"]), float(noise_sd), float(action_sd),
             learner.seed if learner is not None else 0, _ptr(learner._ctr) if learner is not None else None,
@@ -781,6 +798,19 @@ class VecSkillshotGame:
         a = out if out is not None else torch.empty((n_ticks, 2, self.n, 2), dtype=torch.float32,
                                                     device=self.device)
         check(self._L.sk_gen_random_actions(self._h, _ptr(a), int(n_ticks), self._stream()))
+        return a
+
+    def bot_actions(self, kind, out=None):
+        """Both seats' actions float32 [2, N, 2] of the scripted actor `kind`
+        (a name or code, scripted.py) on the current state, the random
+        policy's at the current step counter (sk_env_bot_act): one small
+        launch on the GPU backend, the host loop on the CPU one, the same
+        floats from both.  Advances nothing."""
+        a = out if out is not None else torch.empty((2, self.n, 2), dtype=torch.float32, device=self.device)
+        if (tuple(a.shape) != (2, self.n, 2) or a.dtype != torch.float32 or a.device != self.device or
+                not a.is_contiguous()):
+            raise ValueError(f"out must be contiguous float32 [2, {self.n}, 2] on {self.device}")
+        check(self._L.sk_env_bot_act(self._h, kind_code(kind), _ptr(a), self._stream()))
         return a
 
     def rollout_random(self, n_ticks):
