@@ -146,11 +146,20 @@ int sk_env_clear_counters(sk_env* env, void* stream);
 int sk_env_get_step_counter(const sk_env* env, uint64_t* out);
 int sk_env_set_step_counter(sk_env* env, uint64_t value);
 /* Stream-ordered, capturable: make both device step slots hold the current
- * value (their maximum) and reset the host parity.  A hipGraph captured after
- * this call reads the right value at its first node whatever launches ran
- * between capture and replay, so eager launches and graph replays can be
- * mixed (call it between them).  No reference equivalent (the reference's
- * RNG is np.random's global state, SkillshotGame.py:15). */
+ * value (their maximum) and reset the host parity to 0.  Every launch reads
+ * the slot the host parity names and flips it; a captured launch has its slot
+ * baked in, and a replay moves the device's slots but not the host parity.
+ * So capture right after this call, and call it in BOTH directions:
+ *   - before a replay (eager -> replay, and between two replays when the
+ *     launches replayed since the last call are odd in number): the graph's
+ *     first node reads slot 0, which must be current;
+ *   - after the last replay, before the next eager launch (replay -> eager):
+ *     the eager launch reads the slot of the host parity, which a replay of
+ *     an odd number of launches leaves one value behind.  sk_env_get_step_counter
+ *     does not show that state (it returns the maximum).
+ * With both, eager launches and graph replays mix in any order.  No reference
+ * equivalent (the reference's RNG is np.random's global state,
+ * SkillshotGame.py:15). */
 int sk_env_sync_step_counter(sk_env* env, void* stream);
 
 /* SkillshotGame.game_reset(random_positions) (SkillshotGame.py:168-169 ->

@@ -1710,6 +1710,15 @@ class SkillshotLearner:
         observation and the overlapped tick's horizon each alternate between
         two slots per tick, so an odd count is captured as two graphs, one
         per starting slot, which run() replays alternately.
+
+        Replays and eager calls mix in both directions with no call in
+        between: run() makes both step slots current before it replays and,
+        when its last tick ended in the other slot than the engine's host
+        parity names, again after, so the next eager engine call (step,
+        reset, gen_random_actions, train_ticks, ...) reads the current step
+        counter; it leaves the eager tick's observation buffer and horizon
+        slot where the replays ended (`obs`), and picks up the observation
+        of eager `_tick`s run since (tests/test_graph_handover_gpu.py).
         """
         if self.device.type != "cuda":
             raise RuntimeError("tick_graph needs the GPU engine")
@@ -1801,7 +1810,11 @@ class TickGraph:
         dev = L.device
         # the acting observation alternates between two buffers: tick t reads
         # one and the step writes its reset observations into the other (no
-        # copy); a replay has an even number of ticks, so it ends where it began
+        # copy).  A graph of an even number of ticks ends where it began; an
+        # odd count is two graphs, phase 0 starting in buffer 0 and phase 1
+        # in buffer 1 (see the capture below), and `obs` is _obs[_phase].
+        # _cur is the buffer the next eager tick reads: run() leaves it at
+        # _phase and brings it back there before it replays
         self._obs = [L.prepare_states().clone(), g.new_obs()]
         self._cur = 0
         self.act = torch.empty((2, n, ACTION_DIM), dtype=torch.float32, device=dev)
@@ -2091,6 +2104,11 @@ class TickGraph:
         57.4 us per tick; tools/graph_host_rate.py, profiles/r06at_tickgraph_stream/)."""
         cur = torch.cuda.current_stream(self.L.device)
         cur.wait_stream(self.stream)
+        if self._cur != self._phase:
+            # an odd number of eager ticks since the last replay left the
+            # acting observation in the other buffer than this phase's graph reads
+            self._obs[self._phase].copy_(self._obs[self._cur])
+            self._cur = self._phase
         # both step slots current: the graph of either phase reads its own
         self.L.game_environment.sync_step_counter(ctypes.c_void_p(cur.cuda_stream))
         if self.overlap:  # the first replayed update samples the current count
@@ -2107,6 +2125,17 @@ class TickGraph:
                         it.replay()
             self._phase = (self._phase + self.ticks) % 2
         self.replays += n
+        # hand over to eager calls: the replays moved the device's three
+        # two-slot alternations, the host's fields follow.  The acting
+        # observation and the horizon slot are where the next phase starts;
+        # the engine's host parity is 0 since the sync above, and the last
+        # replayed launch wrote step slot `_phase` (tick j of a run that
+        # starts in phase f writes slot (f + j) % 2, j = 1, 2, ...), so
+        # ending in phase 1 both slots are made current again (one
+        # one-thread launch per run(), none per tick)
+        self._cur = self._hp = self._phase
+        if self._phase:
+            self.L.game_environment.sync_step_counter(ctypes.c_void_p(cur.cuda_stream))
         # host mirrors of the ring (2N rows per tick)
         r, rows = self.L.replay, n * self.ticks * 2 * self.obs.shape[1]
         r.total += rows

@@ -125,9 +125,11 @@ class VecSkillshotGame:
         check(self._L.sk_env_set_step_counter(self._h, int(value)))
 
     def sync_step_counter(self, stream=None):
-        """Stream-ordered: both device step slots take the current value, so
-        graphs captured after this call replay with correct RNG keys after any
-        mix of eager launches (sk_env_sync_step_counter)."""
+        """Stream-ordered: both device step slots take the current value and
+        the host parity returns to 0.  Call it before capturing, before a
+        graph replay, and after the last replay before the next eager call
+        (a replay does not move the host parity): then replays and eager
+        launches keep correct RNG keys in any mix (sk_env_sync_step_counter)."""
         check(self._L.sk_env_sync_step_counter(self._h, stream if stream is not None else self._stream()))
 
     def state_dict(self):
