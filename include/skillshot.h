@@ -486,6 +486,64 @@ int sk_env_act_step_pool_bots(sk_env* env, const uint64_t* nets, int32_t n_actor
                               float* obs_reset, float* ring, int64_t capacity, int64_t* total, uint32_t* arrivals,
                               int64_t* total_copy, void* stream);
 
+/* Match statistics (ABI 13, added: new symbols, nothing existing changes, so
+ * SK_ABI_VERSION stays 13): what each seat did over the ticks its game lived,
+ * tallied in int32 per (game, seat).  A tick counts for a game while the game
+ * is alive at it (live and ticks < tick_limit, the match launch's loop test):
+ * the pre-tick states a match record's row holds in slabs 0 .. lengths - 1.
+ * With p the seat, o the other one, (dx, dy) = pos[o] - pos[p], cheb =
+ * max(|dx|, |dy|) and side / ahead the scripted policy's above
+ * (csrc/sk_stats.hpp, the one text both backends compile), per lived tick:
+ *   SHOTS       +1 if p's cooldown <= 0 (the seat fires this tick)
+ *   IN_FLIGHT   +1 if p's projectile is valid
+ *   ON_TARGET   +1 if ahead > 0 and fabs(side) <= player_size
+ *   UNDER_FIRE  +1 if o's projectile is valid and max(|qx[o] - x[p]|,
+ *               |qy[o] - y[p]|) <= 2 player_size
+ *   AT_WALL     +1 if x < player_speed, y < player_speed, x + player_size +
+ *               player_speed > board_w or y + player_size + player_speed >
+ *               board_h
+ *   PATH        += |x - x_prev| + |y - y_prev| against the previous lived
+ *               tick's position (the first lived tick adds 0)
+ *   DIST_SUM    += cheb
+ *   CLOSEST     = min(CLOSEST, cheb), from INT32_MAX
+ * A stats buffer is int32[SK_N_STATS + 2][2][N], plane-major, seat 1 then
+ * seat 2.  Planes SK_N_STATS and SK_N_STATS + 1 carry x_prev and y_prev
+ * between sk_env_stats_tick calls (x_prev == INT32_MIN: no lived tick yet).
+ * The caller initialises it: every plane 0, CLOSEST INT32_MAX, x_prev
+ * INT32_MIN. */
+#define SK_STAT_SHOTS 0
+#define SK_STAT_IN_FLIGHT 1
+#define SK_STAT_ON_TARGET 2
+#define SK_STAT_UNDER_FIRE 3
+#define SK_STAT_AT_WALL 4
+#define SK_STAT_PATH 5
+#define SK_STAT_DIST_SUM 6
+#define SK_STAT_CLOSEST 7
+#define SK_N_STATS 8
+
+/* sk_env_act_league_bots (rec NULL) or sk_env_act_league_bots_rec with the
+ * statistics tallied in the same launch: every (game, seat) that lived at
+ * least one tick of the call stores its eight words into stats (a DEVICE
+ * buffer as above) once, after its last tick.  A pairing the guard refuses, a
+ * pad game and a game that is not alive when the call starts store nothing,
+ * and planes SK_N_STATS, SK_N_STATS + 1 are left alone (the launch keeps the
+ * previous position in registers): the tallies are those of this call's
+ * ticks.  Everything else is the namesake's.  SK_EINVAL in addition for a
+ * NULL or misaligned stats and where tick_limit * max(board_w, board_h) does
+ * not fit in int32. */
+int sk_env_act_league_stats(sk_env* env, const uint64_t* nets, int32_t n_actors, const int32_t* pairs,
+                            int32_t n_pairs, int32_t block, float* obs2, float* returns, int32_t* lengths,
+                            int32_t* last_half, int32_t n_ticks, int32_t reward_kind, int32_t tick_limit,
+                            int32_t* stats, const sk_match_record* rec, void* stream);
+
+/* One tick of the statistics from the env's current state, for every game
+ * whose alive byte is set (alive uint8[N]; the caller's loop test): the
+ * per-tick form of the launch above, on both backends (HOST pointers on the
+ * CPU one), to be called before the step.  Advances nothing.  SK_EINVAL for
+ * a NULL handle, alive or stats, or stats not 4-byte aligned.
+ * Stream-ordered. */
+int sk_env_stats_tick(sk_env* env, const uint8_t* alive, int32_t* stats, void* stream);
+
 /* sk_env_act_step prepared, not launched (ABI 8): the same arguments
  * (N % 4 == 0, ring given or not) into *job, and the env advances its step
  * slot as if the launch had been issued.  The job is then run, exactly once

@@ -17,6 +17,10 @@ from . import build as _build
 SK_OK, SK_EINVAL, SK_EHIP, SK_ENOMEM, SK_ENODEV = 0, -1, -2, -3, -4
 SK_REWARD_LOOKING, SK_REWARD_SIMPLE = 0, 1
 SK_BOT_STILL, SK_BOT_RANDOM, SK_BOT_AIMER, SK_BOT_CHASER = 1, 2, 3, 4
+# SK_STAT_*: the planes of a stats buffer, int32 [SK_N_STATS + 2][2][N] (the last two: x_prev, y_prev)
+STAT_NAMES = ("shots", "in_flight", "on_target", "under_fire", "at_wall", "path", "dist_sum", "closest")
+SK_N_STATS = len(STAT_NAMES)
+SK_STAT_FAR, SK_STAT_NO_PREV = 2 ** 31 - 1, -2 ** 31  # closest of a game that played no tick; x_prev before one
 ABI_VERSION = 13
 
 # every symbol include/skillshot.h declares
@@ -27,7 +31,7 @@ EXPORTS = (
     "sk_env_set_step_counter", "sk_env_sync_step_counter", "sk_env_reset", "sk_player_move_direction", "sk_player_move_look",
     "sk_player_move_discrete", "sk_player_shoot", "sk_projectile_move", "sk_game_check_collision", "sk_game_tick", "sk_env_features", "sk_env_observe",
     "sk_env_step", "sk_env_step_insert", "sk_env_act_step", "sk_env_act_step_job", "sk_env_act_episode", "sk_env_act_match", "sk_env_act_league", "sk_env_act_match_rec", "sk_env_act_league_rec", "sk_env_act_step_pool", "sk_env_bot_act",
-    "sk_env_act_league_bots", "sk_env_act_league_bots_rec", "sk_env_act_step_pool_bots", "sk_env_step_multi", "sk_env_step_multi_obs", "sk_gen_random_actions", "sk_env_rollout_random",
+    "sk_env_act_league_bots", "sk_env_act_league_bots_rec", "sk_env_act_step_pool_bots", "sk_env_act_league_stats", "sk_env_stats_tick", "sk_env_step_multi", "sk_env_step_multi_obs", "sk_gen_random_actions", "sk_env_rollout_random",
     "sk_actor_packed_bytes", "sk_actor_pack", "sk_actor_forward", "sk_actor_forward_dev",
     "sk_actor_forward_advance", "sk_actor_forward_noise",
     "sk_critic_packed_bytes", "sk_critic_pack", "sk_critic_forward", "sk_target_q",
@@ -146,6 +150,9 @@ def load(build_if_missing=True):
                                         ctypes.POINTER(SkMatchRecord), P], ctypes.c_int),
         "sk_env_act_step_pool_bots": ([P, P, i32, P, i32, i32, i32, P, P, f32, f32, u64, P, P, P, i32, P, P, i32, i32,
                                        i32, P, P, i64, P, P, P, P], ctypes.c_int),
+        "sk_env_act_league_stats": ([P, P, i32, P, i32, i32, P, P, P, P, i32, i32, i32, P,
+                                     ctypes.POINTER(SkMatchRecord), P], ctypes.c_int),
+        "sk_env_stats_tick": ([P, P, P, P], ctypes.c_int),
         "sk_env_act_step_job": ([P, P, P, P, P, f32, f32, u64, P, P, P, i32, P, P, i32, i32, i32, P, P, i64, P, P, P,
                                  ctypes.POINTER(SkStepJob)], ctypes.c_int),
         "sk_env_step_multi": ([P, P, i64, i64, i32, P, P, i64, i32, i32, i32, P], ctypes.c_int),

@@ -26,6 +26,9 @@
 //   k_act_league32_bots, k_act_step_pool32_bots  the league (plain and
 //                    recording) and the pool tick where a seat may be a
 //                    scripted actor (csrc/sk_bot.hpp): no tile for that seat
+//   k_act_league32_stats  the league (plain and recording, nets and scripted
+//                    actors alike) tallying each seat's match statistics
+//                    (csrc/sk_stats.hpp) in wave 0's registers
 //   k_split_pack32   the actor's split pack from its flat fp32 parameters
 // and, at the end, their host launchers (sk_launch_act_*, declared in
 // sk_step.hpp and called by sk_engine.hip and sk_learn32.hip) and C entry
@@ -46,6 +49,7 @@
 #include "sk_mlp.hpp"
 #include "sk_net32.hpp"
 #include "sk_split.hpp"
+#include "sk_stats.hpp"
 #include "sk_step.hpp"
 
 namespace {
@@ -645,11 +649,19 @@ __device__ __forceinline__ void rec_state(const RecArgs& rc, int64_t at, int p, 
 // sAct where the tile would have, ahead of the barrier wave 0 reads sAct
 // behind.  With both seats scripted waves 1-3 only keep the barriers.  Every
 // line of it is under if constexpr as well.
-template <bool REC, bool BOTS = false>
+// STAT (the _stats kernel): wave 0's (game, player) lanes keep the seat's
+// eight statistics (csrc/sk_stats.hpp) and its previous position in registers,
+// update them right behind the loop test from what split_load loaded and the
+// partner lane's position and projectile (the pair exchange, as bot_lane's),
+// and store the eight words once after the loop, into stats int32
+// [SK_N_STATS + 2][2][N]: a lane whose game lived no tick of the call (a pad
+// game among them) stores nothing.  Every line of it is under if constexpr.
+template <bool REC, bool BOTS = false, bool STAT = false>
 __device__ __forceinline__ void match_ticks32(const float* aflat1, const char* apack1, const float* aflat2,
                                               const char* apack2, const sk::StepArgs& a, const sk::Cfg& c,
                                               const MatchArgs& mt, char* smem, const RecArgs* rc = nullptr,
-                                              int rec_b = 0, int rec_k0 = 0, int kind1 = 0, int kind2 = 0) {
+                                              int rec_b = 0, int rec_k0 = 0, int kind1 = 0, int kind2 = 0,
+                                              int32_t* stats = nullptr) {
   float2* sAct = (float2*)(smem + kActorTileLds);
   int* sAlive = (int*)(sAct + 64);
   const int lane = threadIdx.x & 63;
@@ -672,6 +684,7 @@ __device__ __forceinline__ void match_ticks32(const float* aflat1, const char* a
     rec_lane = mine && rec_k0 + (lane >> 1) < rc->per_block;
     rec_j = (int64_t)rec_b * rc->per_block + rec_k0 + (lane >> 1);
   }
+  int32_t sv[SK_N_STATS] = {0, 0, 0, 0, 0, 0, 0, skstat::kFar}, sxp = skstat::kNoPrev, syp = 0;  // STAT only
   for (int t = 0; t < mt.n_ticks; ++t) {
     // both nets' addresses opaque per tick (k_act_episode32's reason, twice over)
     const float *af1 = aflat1, *af2 = aflat2;
@@ -718,6 +731,17 @@ __device__ __forceinline__ void match_ticks32(const float* aflat1, const char* a
           rec_live = alive;
         }
       }
+      if constexpr (STAT) {
+        // the partner lane's position and projectile: every lane of wave 0 takes part in the exchange
+        const int ox = sk::pair_swap(L.pp.x), oy = sk::pair_swap(L.pp.y);
+        const int oqx = sk::pair_swap(L.qq.x), oqy = sk::pair_swap(L.qq.y);
+        if (alive) {
+          const sktrig::SinCos m = skbot::sincos(L.rot, [](double x) { return sk::sincos_lib(x); });
+          const unsigned f = (unsigned)L.mi.y;
+          skstat::tick(sv, sxp, syp, m, L.pp.x, L.pp.y, ox, oy, L.ca.x, ((f >> (8 * L.p)) & 0xff) != 0,
+                       ((f >> (8 * (1 - L.p))) & 0xff) != 0, oqx, oqy, c.psize, c.pspeed, c.W, c.H);
+        }
+      }
     }
     __syncthreads();
     if (!*sAlive) break;  // workgroup-uniform: every game of the workgroup has ended
@@ -738,6 +762,12 @@ __device__ __forceinline__ void match_ticks32(const float* aflat1, const char* a
     __syncthreads();  // this tick's observations are the next tick's acting rows (this workgroup's own stores)
   }
   if (ret) *ret = acc;
+  if constexpr (STAT) {
+    if (mine && sxp != skstat::kNoPrev) {  // gi < n: plane k, seat lane & 1, game gi
+#pragma unroll
+      for (int k = 0; k < SK_N_STATS; ++k) stats[((int64_t)k * 2 + (lane & 1)) * n + gi] = sv[k];
+    }
+  }
   if constexpr (REC) {
     // a game still playing when n_ticks ran out (a break leaves rec_live
     // false in every lane): its state after the last tick, slab slab0 +
@@ -878,6 +908,35 @@ __global__ void __launch_bounds__(kFwdThreads, kEpisodeWaves) k_act_league32_bot
   }
   match_ticks32<REC, true>((const float*)f1, (const char*)k1, (const float*)f2, (const char*)k2, a, c, mt,
                            (char*)smem_sl, &rc, p, ((int)blockIdx.x - p * lg.wgs_per_pair) * 32, b1, b2);
+}
+// The league with the statistics tallied in the launch
+// (sk_env_act_league_stats): k_act_league32_bots' prologue and guard line for
+// line, then match_ticks32<REC, true, true>.  A kernel of its own, so that a
+// call without statistics keeps the kernels it had.  A pairing the guard
+// refuses stores no statistics.
+template <bool REC>
+__global__ void __launch_bounds__(kFwdThreads, kEpisodeWaves) k_act_league32_stats(LeagueArgs lg, sk::StepArgs a,
+                                                                                      sk::Cfg c, MatchArgs mt,
+                                                                                      RecArgs rc, int32_t* stats) {
+  extern __shared__ __attribute__((aligned(16))) float smem_sl[];
+  const int p = (int)blockIdx.x / lg.wgs_per_pair;
+  const int i1 = lg.pairs[2 * p], i2 = lg.pairs[2 * p + 1];
+  uint64_t f1 = 0, k1 = 0, f2 = 0, k2 = 0;
+  if ((unsigned)i1 < (unsigned)lg.n_actors && (unsigned)i2 < (unsigned)lg.n_actors) {
+    f1 = lg.nets[2 * i1];
+    k1 = lg.nets[2 * i1 + 1];
+    f2 = lg.nets[2 * i2];
+    k2 = lg.nets[2 * i2 + 1];
+  }
+  const int b1 = bot_kind(f1, k1), b2 = bot_kind(f2, k2);
+  if (!(b1 || net_ok(f1, k1)) || !(b2 || net_ok(f2, k2))) {
+    const int64_t g = (int64_t)blockIdx.x * 32 + threadIdx.x;
+    if (threadIdx.x < 32 && g < a.n) mt.lengths[g] = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && mt.last_half) *mt.last_half = mt.n_ticks & 1;
+    return;
+  }
+  match_ticks32<REC, true, true>((const float*)f1, (const char*)k1, (const float*)f2, (const char*)k2, a, c, mt,
+                                 (char*)smem_sl, &rc, p, ((int)blockIdx.x - p * lg.wgs_per_pair) * 32, b1, b2, stats);
 }
 
 // The opponent-pool training tick (sk_env_act_step_pool): k_act_step32's tick
@@ -1367,6 +1426,30 @@ int sk_launch_act_league32_bots(const uint64_t* nets, int n_actors, const int32_
     k_act_league32_bots<true><<<G, kFwdThreads, kActMatchLds, st>>>(lg, a, c, mt, rec_args(*rec, block / 32));
   else
     k_act_league32_bots<false><<<G, kFwdThreads, kActMatchLds, st>>>(lg, a, c, mt, RecArgs{});
+  return match_finish(a, lengths, st);
+}
+
+// the league with its statistics (sk_env_act_league_stats): the _bots launcher's checks; stats int32
+// [SK_N_STATS + 2][2][a.n], the tick limit within skstat::fits
+int sk_launch_act_league32_stats(const uint64_t* nets, int n_actors, const int32_t* pairs, int block,
+                                 const sk::StepArgs& a, const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths,
+                                 int32_t* last_half, int n_ticks, int32_t* stats, const sk_match_record* rec,
+                                 hipStream_t st) {
+  static bool attr = false;
+  if (!attr) {
+    set_lds32(k_act_league32_stats<false>, kActMatchLds);
+    set_lds32(k_act_league32_stats<true>, kActMatchLds);
+    attr = true;
+  }
+  if (!seating_ok(nets, n_actors, pairs, block, a) || !rec_ok(rec, a.n / block, block)) return SK_EINVAL;
+  if (!stats || (((uintptr_t)stats) & 3) || !skstat::fits(a.tick_limit, c.W, c.H)) return SK_EINVAL;
+  const unsigned G = (unsigned)(a.n / 32);
+  const MatchArgs mt{obs2, returns, lengths, last_half, n_ticks};
+  const LeagueArgs lg{nets, pairs, n_actors, block / 32};
+  if (rec)
+    k_act_league32_stats<true><<<G, kFwdThreads, kActMatchLds, st>>>(lg, a, c, mt, rec_args(*rec, block / 32), stats);
+  else
+    k_act_league32_stats<false><<<G, kFwdThreads, kActMatchLds, st>>>(lg, a, c, mt, RecArgs{}, stats);
   return match_finish(a, lengths, st);
 }
 

@@ -40,6 +40,7 @@
 #include "sk_host.hpp"
 #include "sk_multi_plan.hpp"
 #include "sk_range.hpp"
+#include "sk_stats.hpp"
 #include "sk_step.hpp"
 
 
@@ -430,6 +431,39 @@ __global__ void __launch_bounds__(kStepBlock) k_bot_act(View v, int64_t n, int k
   const double rot = reinterpret_cast<const double*>(v.rot)[hc];
   const float2 a = bot_lane(kind, p, pp, rot, c, seed, (uint64_t)(env_offset + i), step_read(sref));
   if (in) actions[(int64_t)p * n + i] = a;
+}
+
+// sk_env_stats_tick: one tick of the match statistics (csrc/sk_stats.hpp) from
+// the current state, k_bot_act's lanes (the partner's position and projectile
+// through the pair exchange, which every lane joins).  stats int32
+// [SK_N_STATS + 2][2][n]: a lane whose game's alive byte is set reads its ten
+// words, updates them and stores them back; every other lane (one past the
+// end among them, which reads game 0) stores nothing.
+__global__ void __launch_bounds__(kStepBlock) k_stats_tick(View v, int64_t n, const uint8_t* __restrict__ alive,
+                                                           int32_t* __restrict__ stats, Cfg c) {
+  const int64_t gt = (int64_t)blockIdx.x * kStepBlock + threadIdx.x, i = gt >> 1;
+  const int p = (int)(gt & 1);
+  const bool in = i < n;
+  const int64_t ic = in ? i : 0, hc = 2 * ic + p;
+  const int2 pp = reinterpret_cast<const int2*>(v.pos)[hc];
+  const int2 qq = reinterpret_cast<const int2*>(v.qpos)[hc];
+  const int2 ca = reinterpret_cast<const int2*>(v.qcdage)[hc];
+  const double rot = reinterpret_cast<const double*>(v.rot)[hc];
+  const unsigned f = (unsigned)v.misc[ic].y;
+  const int ox = pair_swap(pp.x), oy = pair_swap(pp.y), oqx = pair_swap(qq.x), oqy = pair_swap(qq.y);
+  if (!in || !alive[ic]) return;
+  int32_t* const w = stats + (int64_t)p * n + ic;  // word k of this (seat, game): w[2 n k]
+  int32_t s[SK_N_STATS];
+#pragma unroll
+  for (int k = 0; k < SK_N_STATS; ++k) s[k] = w[2 * n * k];
+  int32_t xp = w[2 * n * SK_N_STATS], yp = w[2 * n * (SK_N_STATS + 1)];
+  const sktrig::SinCos m = skbot::sincos(rot, [](double x) { return sincos_lib(x); });
+  skstat::tick(s, xp, yp, m, pp.x, pp.y, ox, oy, ca.x, ((f >> (8 * p)) & 0xff) != 0, ((f >> (8 * (1 - p))) & 0xff) != 0,
+               oqx, oqy, c.psize, c.pspeed, c.W, c.H);
+#pragma unroll
+  for (int k = 0; k < SK_N_STATS; ++k) w[2 * n * k] = s[k];
+  w[2 * n * SK_N_STATS] = xp;
+  w[2 * n * (SK_N_STATS + 1)] = yp;
 }
 
 __global__ void __launch_bounds__(kBlock) k_reset(View v, int64_t n, const uint8_t* mask, int random,
@@ -1342,6 +1376,30 @@ int sk_env_act_league_bots_rec(sk_env* e, const uint64_t* nets, int32_t n_actors
                     tick_limit, true, rec, stream, true);
 }
 
+// sk_env_act_league_stats: act_league's checks (a record when one is given), then the stats buffer and the
+// tallies' range, the _stats kernels
+int sk_env_act_league_stats(sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
+                            int32_t block, float* obs2, float* returns, int32_t* lengths, int32_t* last_half,
+                            int32_t n_ticks, int32_t reward_kind, int32_t tick_limit, int32_t* stats,
+                            const sk_match_record* rec, void* stream) {
+  SK_CHECK_ENV(e);
+  StepArgs a;
+  int rc = seating_check(e, nets, n_actors, pairs, n_pairs, block);
+  if (rc == SK_OK) rc = match_out_check(obs2, returns, lengths, last_half, n_ticks);
+  if (rc == SK_OK) rc = match_step_args(e, obs2, returns, reward_kind, tick_limit, a);
+  if (rc == SK_OK && rec) rc = rec_check(rec, n_pairs, block, n_ticks, returns);
+  if (rc != SK_OK) return rc;
+  if (!stats || (((uintptr_t)stats) & 3)) return fail(SK_EINVAL, "stats is NULL or not 4-byte aligned");
+  if (!skstat::fits(tick_limit, e->cfg.board_w, e->cfg.board_h))
+    return fail(SK_EINVAL, "tick_limit * max(board_w, board_h) must fit in int32 for the statistics");
+  if (e->host) return fail(SK_EINVAL, "sk_env_act_league_stats runs on the GPU backend");
+  rc = sk_launch_act_league32_stats(nets, n_actors, pairs, block, a, e->dcfg, obs2, returns, lengths, last_half,
+                                    n_ticks, stats, rec, (hipStream_t)stream);
+  if (rc != SK_OK) return fail(rc, "k_act_league32_stats launch failed");
+  e->parity ^= 1;
+  return SK_OK;
+}
+
 // sk_env_act_step_pool and sk_env_act_step_pool_bots
 static int act_step_pool(sk_env* e, const uint64_t* nets, int32_t n_actors, const int32_t* pairs, int32_t n_pairs,
                          int32_t block, int32_t noisy_actor, const float* acting_obs, float* actions, float noise_sd,
@@ -1639,6 +1697,19 @@ int sk_env_bot_act(sk_env* e, int32_t kind, float* actions, void* stream) {
   k_bot_act<<<step_grid(2 * (int64_t)e->n), kStepBlock, 0, (hipStream_t)stream>>>(
       e->view, e->n, kind, reinterpret_cast<float2*>(actions), e->dcfg, e->seed, e->env_offset,
       StepRef{e->d_step, e->parity});
+  SK_LAUNCH_CHECK();
+  return SK_OK;
+}
+
+// one tick of the match statistics (csrc/sk_stats.hpp) from the current state, for the games whose alive byte is set:
+// k_stats_tick, two lanes per game like k_bot_act; advances nothing
+int sk_env_stats_tick(sk_env* e, const uint8_t* alive, int32_t* stats, void* stream) {
+  SK_CHECK_ENV(e);
+  if (!alive || !stats) return fail(SK_EINVAL, "alive or stats is NULL");
+  if (((uintptr_t)stats) & 3) return fail(SK_EINVAL, "stats must be 4-byte aligned");
+  if (e->host) return skh::stats_tick(*e->host, alive, stats), SK_OK;
+  k_stats_tick<<<step_grid(2 * (int64_t)e->n), kStepBlock, 0, (hipStream_t)stream>>>(e->view, e->n, alive, stats,
+                                                                                     e->dcfg);
   SK_LAUNCH_CHECK();
   return SK_OK;
 }

@@ -29,6 +29,7 @@
 
 #include "../../include/skillshot.h"
 #include "sk_bot.hpp"
+#include "sk_stats.hpp"
 #include "sk_host.hpp"
 
 namespace skh {
@@ -572,6 +573,34 @@ void bot_act(Host& h, int kind, float* actions) {
                                            h.cfg.look_speed, h.cfg.player_size, r[2 * p], r[2 * p + 1]);
         actions[2 * ((int64_t)p * n + i)] = a.move;
         actions[2 * ((int64_t)p * n + i) + 1] = a.look;
+      }
+    }
+  });
+}
+
+// sk_env_stats_tick: the match statistics (sk_stats.hpp, the text the device
+// compiles) of both seats of every game whose alive byte is set, on the
+// current state
+void stats_tick(Host& h, const uint8_t* alive, int32_t* stats) {
+  const int64_t n = h.n;
+  const auto lib = [](double x) { return sktrig::SinCos{std::sin(x), std::cos(x)}; };
+  for_envs(h, [&](int64_t lo, int64_t hi, sk_counters&) {
+    for (int64_t i = lo; i < hi; ++i) {
+      if (!alive[i]) continue;
+      Env e;
+      load(h, i, e);
+      for (int p = 0; p < 2; ++p) {
+        const int o = 1 - p;
+        int32_t* const w = stats + (int64_t)p * n + i;  // word k of this (seat, game): w[2 n k]
+        int32_t s[SK_N_STATS];
+        for (int k = 0; k < SK_N_STATS; ++k) s[k] = w[2 * n * k];
+        int32_t xp = w[2 * n * SK_N_STATS], yp = w[2 * n * (SK_N_STATS + 1)];
+        skstat::tick(s, xp, yp, skbot::sincos(e.rot[p], lib), e.px[p], e.py[p], e.px[o], e.py[o], e.qcd[p],
+                     e.qvalid[p] != 0, e.qvalid[o] != 0, e.qx[o], e.qy[o], h.cfg.player_size, h.cfg.player_speed,
+                     h.cfg.board_w, h.cfg.board_h);
+        for (int k = 0; k < SK_N_STATS; ++k) w[2 * n * k] = s[k];
+        w[2 * n * SK_N_STATS] = xp;
+        w[2 * n * (SK_N_STATS + 1)] = yp;
       }
     }
   });

@@ -44,6 +44,8 @@ void step(Host& h, const float* actions, float* obs, float* reward, int kind, ui
 void gen_random_actions(Host& h, float* actions, int n_ticks);
 // sk_env_bot_act on host planes: actions float[2][N][2]
 void bot_act(Host& h, int kind, float* actions);
+// sk_env_stats_tick on host planes: alive uint8[N], stats int32[SK_N_STATS + 2][2][N]
+void stats_tick(Host& h, const uint8_t* alive, int32_t* stats);
 void rollout_random(Host& h, int n_ticks, int tick_limit);
 // sk_render_states on host planes (validated by the caller): out uint8[m][W][H]
 void render(const sk_config& cfg, const sk_state_view& v, const int64_t* ids, int64_t m, uint8_t* out);

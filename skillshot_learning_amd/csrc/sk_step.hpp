@@ -548,6 +548,11 @@ int sk_launch_act_step_pool32(const uint64_t* nets, int n_actors, const int32_t*
 int sk_launch_act_league32_bots(const uint64_t* nets, int n_actors, const int32_t* pairs, int block,
                                 const sk::StepArgs& a, const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths,
                                 int32_t* last_half, int n_ticks, const sk_match_record* rec, hipStream_t st);
+// k_act_league32_stats (csrc/sk_act32.hpp): the league with scripted actors, tallying the match statistics
+int sk_launch_act_league32_stats(const uint64_t* nets, int n_actors, const int32_t* pairs, int block,
+                                 const sk::StepArgs& a, const sk::Cfg& c, float* obs2, float* returns, int32_t* lengths,
+                                 int32_t* last_half, int n_ticks, int32_t* stats, const sk_match_record* rec,
+                                 hipStream_t st);
 int sk_launch_act_step_pool32_bots(const uint64_t* nets, int n_actors, const int32_t* pairs, int block,
                                    int noisy_actor, float* act_out, float sd, float action_sd, uint64_t seed,
                                    uint64_t* call_ctr, const sk::StepArgs& a, const sk::Cfg& c, hipStream_t st);

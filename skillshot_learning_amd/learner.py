@@ -846,6 +846,46 @@ def _match_summary(games, wins, losses, draws, ticks_sum, ret_self, ret_opp, sea
     return d
 
 
+# The match statistics (include/skillshot.h SK_STAT_*, csrc/sk_stats.hpp) as evaluate and league report them.  A
+# seat's games reduce to _N_STAT_SUMS numbers: the sums of planes 0 .. 6, the sum and the count of the per-game
+# `closest` over games that played a tick, and the ticks played.
+_N_STAT_SUMS = 10
+STAT_REPORT = ("shots", "in_flight", "on_target", "under_fire", "at_wall", "path", "mean_distance", "closest")
+
+
+def _stats_sums(stats, played):
+    """stats: int32 [SK_N_STATS + 2, 2, P, G] (a view of a raw buffer: P
+    blocks of G games); played: int [P, G], the ticks each game played.  The
+    seats' sums, reduced in int64: fp64 [P, 2, _N_STAT_SUMS] on the device
+    (exact: every sum stays far below 2^53)."""
+    from ._capi import SK_N_STATS
+    s = stats[:SK_N_STATS].long()
+    seen = (played > 0)[None].expand(2, -1, -1)
+    tk = played.long().sum(-1)[None].expand(2, -1)
+    out = torch.cat([s[:SK_N_STATS - 1].sum(-1), torch.where(seen, s[SK_N_STATS - 1], 0).sum(-1)[None],
+                     seen.sum(-1)[None], tk[None]], 0)
+    return out.permute(2, 1, 0).double()
+
+
+def _stats_report(v):
+    """_stats_sums' numbers of one seat (array-like [..., _N_STAT_SUMS]) as
+    the reported values, a dict by name of arrays [...]: shots a count, the
+    four flags their share of the ticks played, path and mean_distance per
+    tick played, closest the mean of the per-game minima over games that
+    played a tick (nan where no tick was played)."""
+    v = np.asarray(v, dtype=np.float64)
+    tk, cn = v[..., 9], v[..., 8]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d = {name: np.where(tk > 0, v[..., k] / tk, np.nan) for k, name in enumerate(STAT_REPORT[:7]) if k}
+        d["closest"] = np.where(cn > 0, v[..., 7] / cn, np.nan)
+    d["shots"] = v[..., 0].astype(np.int64)
+    return {name: d[name] for name in STAT_REPORT}
+
+
+def _stats_dict(v):
+    return {k: (int(x) if k == "shots" else float(x)) for k, x in _stats_report(v).items()}
+
+
 def bradley_terry_elo(score, n):
     """Elo ratings of K actors from their pairwise results, by the maximum
     likelihood fit of the Bradley-Terry model P(i beats j) = p_i / (p_i +
@@ -1155,7 +1195,7 @@ class SkillshotLearner:
 
     # ------------------------------------------------------------ evaluation
     def evaluate(self, opponent=None, games=None, swap_sides=True, tick_limit=None, reward="looking", seed=None,
-                 record=0):
+                 record=0, stats=False):
         """Head-to-head evaluation: this learner's actor against `opponent`,
         both deterministic (no exploration noise), over `games` whole games.
 
@@ -1179,6 +1219,24 @@ class SkillshotLearner:
                   (record.py: states, actions, rewards, boards); both legs'
                   slab 0 are the same start states.  The tallies are those of
                   the same call without it, on either path.
+        stats     also report what each side DID: every leg and the total
+                  gain stats = dict(mine={...}, theirs={...}), by name: shots
+                  (fired, a count), in_flight, on_target, under_fire, at_wall
+                  (the share of the ticks played at which the side's own
+                  projectile flew, it faced its opponent within a player's
+                  width, an opposing projectile was within two widths of it,
+                  a full-speed move along an axis would have left the board),
+                  path (distance walked, |dx| + |dy|) and mean_distance (the
+                  Chebyshev distance between the players) per tick played,
+                  closest (the mean over games of that distance's minimum).
+                  Definitions: include/skillshot.h SK_STAT_*.  A kernel-path
+                  leg is then a league launch of one pairing that tallies them
+                  in registers (act_league(stats=True)); a loop-path leg asks
+                  stats_tick before every step.  Every other field is the
+                  number the call without stats returns; combines with record.
+                  The result also gains stats_raw, per leg the tallied words
+                  on the device: int32 [SK_N_STATS, 2 (seat 1, seat 2), games],
+                  plane _capi.STAT_NAMES.index(name).
 
         The games run on a dedicated evaluation env (created on first use,
         kept per (games, tick_limit, seed)), rewound at every call: the same
@@ -1210,15 +1268,22 @@ class SkillshotLearner:
         g.step_counter = 0
         g.reset(random_positions=self.use_random_start)
         start = g.state_dict() if swap_sides else None
-        rows, records = [], []
+        rows, records, raws = [], [], []
         for seat in ((1, 2) if swap_sides else (1,)):
             if seat == 2:
                 g.load_state_dict(start)
             a1, a2 = (mine, theirs) if seat == 1 else (theirs, mine)
-            rows.append(self._match_leg(g, a1, a2, seat, limit, reward, use_kernel, record=r, records=records))
-        flat = torch.stack(rows).cpu()  # the one host read: six scalars per leg
-        legs = [_match_summary(n, *flat[k].tolist(), seat=k + 1) for k in range(len(rows))]
-        total = _match_summary(n * len(rows), *flat.sum(0).tolist())
+            rows.append(self._match_leg(g, a1, a2, seat, limit, reward, use_kernel, record=r, records=records,
+                                        stats=bool(stats)))
+            if stats:
+                raws.append(self._stats_raw[:, :, 0])
+        flat = torch.stack(rows).cpu()  # the one host read: six scalars per leg (and the statistics' sums)
+        legs = [_match_summary(n, *flat[k, :6].tolist(), seat=k + 1) for k in range(len(rows))]
+        total = _match_summary(n * len(rows), *flat[:, :6].sum(0).tolist())
+        if stats:
+            for d, v in zip(legs + [total], list(flat[:, 6:].numpy()) + [flat[:, 6:].sum(0).numpy()]):
+                d["stats"] = dict(mine=_stats_dict(v[:_N_STAT_SUMS]), theirs=_stats_dict(v[_N_STAT_SUMS:]))
+            total["stats_raw"] = raws
         total["legs"] = legs
         if r:
             total["records"] = records
@@ -1233,7 +1298,7 @@ class SkillshotLearner:
             raise ValueError(f"record must lie in [0, {games}], the games played")
         return int(record)
 
-    def league(self, actors, games=None, tick_limit=None, reward="looking", seed=None, record=0):
+    def league(self, actors, games=None, tick_limit=None, reward="looking", seed=None, record=0, stats=False):
         """Round robin of K actors: every ORDERED pairing (i, j), i != j,
         plays `games` whole games, i in seat 1 and j in seat 2, all from
         evaluate's start states (the same `games`, tick_limit and seed give
@@ -1251,6 +1316,15 @@ class SkillshotLearner:
                 `record` rows per pairing in the pairings' order, whose
                 `pairs` names each row's (i, j) and whose `games` its game
                 among evaluate's start states
+        stats   also report what the actors DID (evaluate's `stats`, the same
+                names and units): the result gains stats[name], a [K][K] table
+                of seat 1's values in pairing (i, j), opponent_stats[name],
+                seat 2's, and actor_stats[name][i], actor i over all its
+                games from both seats.  Tallied in the one launch
+                (act_league(stats=True)) or by stats_tick on the pair-by-pair
+                path; every other entry is unchanged.  stats_raw: the
+                tallied words on the device, int32 [SK_N_STATS, 2 (seat 1,
+                seat 2), K (K - 1) pairings in their order, games].
 
         With the fp32 acting kernel on a GPU all K (K - 1) pairings play in
         ONE launch (VecSkillshotGame.act_league) on a league env of K (K - 1)
@@ -1295,12 +1369,13 @@ class SkillshotLearner:
         use_kernel = (self._match_kernel_usable() and all(p[1] is not None for p in players) and
                       os.environ.get("SK_LEAGUE_KERNEL", "1") != "0")
         if use_kernel:
-            rows = self._league_launch(g, [p[1] for p in players], pairs, n, limit, reward, record=r)
+            rows = self._league_launch(g, [p[1] for p in players], pairs, n, limit, reward, record=r,
+                                       stats=bool(stats))
             if r:
                 rows, rec = rows
         else:
             start = g.state_dict()
-            legs, recs = [], []
+            legs, recs, raws = [], [], []
             block = 32 * ((n + 31) // 32)
             for k, (i, j) in enumerate(pairs):
                 # a scripted random seat draws by the game's global id: pairing k's games carry the ids they
@@ -1313,13 +1388,18 @@ class SkillshotLearner:
                 legs.append(self._match_leg(gk, players[i], players[j], 1, limit, reward,
                                             self._match_kernel_usable() and players[i][1] is not None and
                                             players[j][1] is not None and
-                                            os.environ.get("SK_MATCH_KERNEL", "1") != "0", record=r, records=recs))
+                                            os.environ.get("SK_MATCH_KERNEL", "1") != "0", record=r, records=recs,
+                                            stats=bool(stats)))
+                if stats:
+                    raws.append(self._stats_raw)
             rows = torch.stack(legs)
+            if stats:
+                self._stats_raw = torch.cat(raws, 2)
             if r:
                 from .record import MatchRecord
                 rec = MatchRecord.concat(recs, pairs)
-        flat = rows.cpu().numpy()  # the one host read: six scalars per pairing
-        tab = np.zeros((6, K, K))
+        flat = rows.cpu().numpy()  # the one host read: six scalars per pairing (and the statistics' sums)
+        tab = np.zeros((flat.shape[1], K, K))
         for k, (i, j) in enumerate(pairs):
             tab[:, i, j] = flat[k]
         sw, sl, sd = tab[0], tab[1], tab[2]
@@ -1336,18 +1416,33 @@ class SkillshotLearner:
                    opponent_mean_return=(tab[5] / n).tolist(), wins=ints(wins), draws=ints(draws),
                    score=score.tolist(), elo=elo.tolist(),
                    ranking=sorted(range(K), key=lambda i: (-elo[i], i)))
+        if stats:
+            s1 = np.moveaxis(tab[6:6 + _N_STAT_SUMS], 0, -1)  # [K, K, sums]: seat 1 of pairing (i, j)
+            s2 = np.moveaxis(tab[6 + _N_STAT_SUMS:], 0, -1)   # seat 2 of pairing (i, j)
+            diag = np.eye(K, dtype=bool)
+
+            def table(v):
+                return {k: np.where(diag, 0, a).tolist() for k, a in _stats_report(v).items()}
+
+            res["stats"], res["opponent_stats"] = table(s1), table(s2)
+            res["actor_stats"] = {k: a.tolist() for k, a in _stats_report(s1.sum(1) + s2.sum(0)).items()}
+            res["stats_raw"] = self._stats_raw
         if r:
             res["record"] = rec
         return res
 
-    def _league_launch(self, g, kernels, pairs, games, limit, reward, record=0):
+    def _league_launch(self, g, kernels, pairs, games, limit, reward, record=0, stats=False):
         """league's pairings in one launch from env g's current (start) state:
         fp64 [P, 6] on the device, _match_leg's tallies for seat 1 of every
         pairing.  The reward sums are taken as _match_leg takes them, an fp32
         sum over a [2, games] buffer per pairing, so both paths of league
         return the same numbers.  record > 0: (the tallies, the launch's
         MatchRecord of `record` rows per pairing, its `games` counted within
-        the pairing as the pair-by-pair path counts them)."""
+        the pairing as the pair-by-pair path counts them).  stats: the launch
+        tallies the match statistics (act_league(stats=True)), and each row
+        becomes [P, 6 + 2 _N_STAT_SUMS]: seat 1's sums (_stats_sums), then
+        seat 2's, reduced on the device beside the tallies; the raw words of
+        the games played are left in self._stats_raw."""
         from .vec_env import PLANES, VecSkillshotGame
         P, block = len(pairs), 32 * ((games + 31) // 32)
         envs = self.__dict__.setdefault("_league_envs", {})
@@ -1368,7 +1463,7 @@ class SkillshotLearner:
         obs, _ = g.observe(reward=reward)
         lg._league_obs[:, :, :games] = obs[:, None]
         m = lg.act_league(kernels, pairs, block, lg._league_obs, n_ticks=limit, reward=reward,
-                          out=getattr(lg, "_league_bufs", None), record=record)
+                          out=getattr(lg, "_league_bufs", None), record=record, stats=bool(stats))
         rec = m.pop("record", None)
         lg._league_bufs = m
         w = lg.winner_id.view(P, block)[:, :games]
@@ -1382,6 +1477,10 @@ class SkillshotLearner:
         sums = torch.stack(sums).view(P, 2).double()
         tallies = torch.stack([(w == 2).sum(1).double(), (w == 1).sum(1).double(), (w == 0).sum(1).double(),
                                ticks.sum(1).double(), sums[:, 0], sums[:, 1]], 1)
+        if stats:
+            raw = m["stats"].view(-1, 2, P, block)[..., :games]
+            tallies = torch.cat([tallies, _stats_sums(raw, m["lengths"].view(P, block)[:, :games]).reshape(P, -1)], 1)
+            self._stats_raw = raw[:raw.shape[0] - 2].clone()  # int32 [SK_N_STATS, 2, P, games], for the caller
         if rec is None:
             return tallies
         rec.games = rec.games % block
@@ -1407,21 +1506,28 @@ class SkillshotLearner:
         return (self.precision == "fp32" and self.device.type == "cuda" and
                 getattr(self.actor_kernel, "fused_act_step", False))
 
-    def _match_leg(self, g, a1, a2, seat, limit, reward, use_kernel, record=0, records=None):
+    def _match_leg(self, g, a1, a2, seat, limit, reward, use_kernel, record=0, records=None, stats=False):
         """one leg on env g from its current state, seat 1 acting from a1 and
         seat 2 from a2 (each a pair of _match_actors): six 0-d fp64 tallies on
         the device, from the point of view of the player in `seat` — wins,
         losses, draws, the games' ticks, the own and the other seat's reward
         sums (fp32 sums over the games).  record > 0: the MatchRecord of the
-        leg's first `record` games is appended to `records`."""
-        if use_kernel and (isinstance(a1[1], ScriptedActor) or isinstance(a2[1], ScriptedActor)):
-            # a scripted seat: the leg as a league of one pairing (act_match seats two nets)
-            row = self._league_launch(g, [a1[1], a2[1]], [(0, 1)], g.n, limit, reward, record=record)
+        leg's first `record` games is appended to `records`.  stats: behind
+        the six tallies come the match statistics' sums (_stats_sums) of the
+        player in `seat`, then the other seat's; the leg's raw words are left
+        in self._stats_raw, int32 [SK_N_STATS, 2 (seat 1, seat 2), 1, games]."""
+        swap = [1, 0, 2, 3, 5, 4]
+        if stats:
+            swap += list(range(6 + _N_STAT_SUMS, 6 + 2 * _N_STAT_SUMS)) + list(range(6, 6 + _N_STAT_SUMS))
+        if use_kernel and (stats or isinstance(a1[1], ScriptedActor) or isinstance(a2[1], ScriptedActor)):
+            # a scripted seat, or statistics: the leg as a league of one pairing (act_match seats two nets and
+            # tallies nothing)
+            row = self._league_launch(g, [a1[1], a2[1]], [(0, 1)], g.n, limit, reward, record=record, stats=stats)
             if record:
                 row, rec = row
                 rec.pairs = None
                 records.append(rec)
-            return row[0] if seat == 1 else row[0][[1, 0, 2, 3, 5, 4]]
+            return row[0] if seat == 1 else row[0][swap]
         obs, _ = g.observe(reward=reward)
         if use_kernel:
             m = g.act_match(a1[1], a2[1], obs, n_ticks=limit, reward=reward,
@@ -1434,12 +1540,22 @@ class SkillshotLearner:
             if record:
                 from .record import MatchRecord
                 rec = MatchRecord.allocate(g.tick_limit + 1, torch.arange(record), g.config, g.device)
-            ret, winner, ticks = self._match_loop(g, a1[0], a2[0], obs, reward, record=rec)
+            if stats:
+                buf = g.new_stats(out=getattr(g, "_match_stats", None))
+                g._match_stats = buf
+                ret, winner, ticks, played = self._match_loop(g, a1[0], a2[0], obs, reward, record=rec, stats=buf)
+            else:
+                ret, winner, ticks = self._match_loop(g, a1[0], a2[0], obs, reward, record=rec)
         if rec is not None:
             records.append(rec)
         o = match_outcomes(winner, seat)
-        return torch.stack([v.double() for v in (o["wins"], o["losses"], o["draws"], ticks.sum(),
-                                                 ret[seat - 1].sum(), ret[2 - seat].sum())])
+        row = torch.stack([v.double() for v in (o["wins"], o["losses"], o["draws"], ticks.sum(),
+                                                ret[seat - 1].sum(), ret[2 - seat].sum())])
+        if stats:
+            sums = _stats_sums(buf.view(buf.shape[0], 2, 1, g.n), played.view(1, g.n))[0]
+            row = torch.cat([row, sums[seat - 1], sums[2 - seat]])
+            self._stats_raw = buf[:buf.shape[0] - 2].view(-1, 2, 1, g.n).clone()
+        return row
 
     def _match_actors(self, opponent):
         """(callable obs [M, 12] -> actions [M, 2], ActorKernel32 or None) of
@@ -1504,7 +1620,7 @@ class SkillshotLearner:
         return pair(net, ent["kernel"])
 
     @torch.no_grad()
-    def _match_loop(self, g, act1, act2, obs, reward, record=None):
+    def _match_loop(self, g, act1, act2, obs, reward, record=None, stats=None):
         """one leg tick by tick on env g: seat 1 acts with act1, seat 2 with
         act2; returns (fp32 reward sums [2, N] over each game's own ticks, the
         games' final winner_id and ticks).  step(auto_reset=False) keeps
@@ -1513,7 +1629,10 @@ class SkillshotLearner:
         (a MatchRecord over games of g): filled as the one-launch kernels fill
         theirs, for the same reason — a row takes its game's pre-tick state,
         actions and rewards only while the game lives, and the post-tick
-        state at the tick it ends."""
+        state at the tick it ends.  stats (a buffer of g.new_stats()): every
+        tick's state is tallied into it before the step, for the games alive
+        at that tick (g.stats_tick); then a fourth value is returned, the
+        ticks each game played."""
         n, dev = g.n, g.device
         alive = g.game_live & (g.ticks < g.tick_limit)
         acc = torch.zeros((2, n), dtype=torch.float32, device=dev)
@@ -1529,9 +1648,12 @@ class SkillshotLearner:
                 act = torch.stack((act1(obs[0]), act2(obs[1])))
             if record is not None:
                 ar = record.loop_before(g, t, alive)
+            if stats is not None:
+                g.stats_tick(stats, alive)
             out = g.step(act, obs=True, reward=reward, auto_reset=False)
             if record is not None:
                 record.loop_after(g, t, ar, act, out["reward"], out["done"])
+            if record is not None or stats is not None:
                 played += alive.int()
             acc = torch.where(alive[None, :], acc + out["reward"], acc)
             newly = alive & out["done"].bool()
@@ -1543,6 +1665,8 @@ class SkillshotLearner:
         if record is not None:
             record.lengths.copy_(played[record.games])
             record.ticks_run = t
+        if stats is not None:
+            return acc, winner, ticks, played
         return acc, winner, ticks
 
     # ------------------------------------------------------------ on-disk formats (persist.py)

@@ -557,12 +557,13 @@ class VecSkillshotGame:
         return rec
 
     def _match_launch(self, what, plain, recording, seats, blocks, block, start_obs, n_ticks, reward, o, resume,
-                      record):
+                      record, stats=None):
         """act_match's / act_league's launch over `blocks` blocks of `block`
         games: the C symbol `plain`, or `recording` (plain's arguments and the
         record) while the record has slabs left, with the seating's arguments
-        `seats` between the handle and the shared ones.  Returns act_match's
-        dict."""
+        `seats` between the handle and the shared ones.  stats (a buffer of
+        new_stats): sk_env_act_league_stats instead, which takes the buffer
+        and the record or NULL.  Returns act_match's dict."""
         if resume and (o.get("returns") is None or o.get("lengths") is None):
             raise ValueError(f"resume needs the dict a previous {what} returned as out")
         T = int(self.tick_limit if n_ticks is None else n_ticks)
@@ -578,7 +579,14 @@ class VecSkillshotGame:
         rec = self._match_record(record, blocks, block, resume)
         T_rec = min(T, rec.slabs - 1 - rec.ticks_run) if rec is not None else 0
         outs = (_ptr(obs2), _ptr(ret), _ptr(call_ln), _ptr(o.get("last_half")))
-        if T_rec >= 1:
+        if stats is not None:
+            st = rec.c_struct(rec.ticks_run) if T_rec >= 1 else None
+            check(self._L.sk_env_act_league_stats(self._h, *seats, *outs, T_rec if st is not None else T,
+                                                  REWARD_KINDS[reward], self.tick_limit, _ptr(stats),
+                                                  ctypes.byref(st) if st is not None else None, self._stream()))
+            if st is not None:
+                rec.ticks_run += T_rec
+        elif T_rec >= 1:
             st = rec.c_struct(rec.ticks_run)
             check(recording(self._h, *seats, *outs, T_rec, REWARD_KINDS[reward], self.tick_limit, ctypes.byref(st),
                             self._stream()))
@@ -592,6 +600,8 @@ class VecSkillshotGame:
             total.copy_(call_ln)
         res = dict(lengths=total, returns=ret, obs=obs, obs2=obs2, call_lengths=call_ln,
                    last_half=o.get("last_half"))
+        if stats is not None:
+            res["stats"] = stats
         if rec is not None:
             torch.index_select(total, 0, rec.games, out=rec.lengths)
             res["record"] = rec
@@ -632,7 +642,7 @@ class VecSkillshotGame:
                                   self.n, start_obs, n_ticks, reward, out or {}, resume, record)
 
     def act_league(self, actors, pairs, block, start_obs, n_ticks=None, reward="looking", out=None, resume=False,
-                   record=None):
+                   record=None, stats=False):
         """Every pairing of a league in ONE launch (sk_env_act_league):
         the env holds len(pairs) blocks of `block` games (a multiple of 32),
         and the games of block p play act_match's match with seat 1 acting
@@ -652,9 +662,19 @@ class VecSkillshotGame:
         `actors` may hold ScriptedActors (scripted.py): their seats run no
         forward, the launch (sk_env_act_league_bots) computes the policy on
         each tick's state itself and a record keeps the policy's actions; a
-        list of nets alone goes through sk_env_act_league as before."""
+        list of nets alone goes through sk_env_act_league as before.
+        stats=True: the launch (sk_env_act_league_stats, nets and scripted
+        seats alike) also tallies what each seat did over the ticks its game
+        lived (include/skillshot.h, csrc/sk_stats.hpp): the returned dict
+        gains `stats`, the raw int32 [SK_N_STATS + 2, 2, N] buffer of
+        new_stats (out["stats"] is initialised again and reused), whose words
+        stats_tick before every step of the per-tick loop would have counted.
+        The tallies are one call's, so stats does not combine with resume;
+        every other entry is what the call without stats returns."""
         if self.is_cpu:
             raise SkillshotError("act_league runs on the GPU backend (SkillshotLearner.league loops on the CPU one)")
+        if stats and resume:
+            raise ValueError("act_league(stats=True) tallies one call's ticks: it does not combine with resume")
         o = out or {}
         actors, plist, block = self._seating("act_league", actors, pairs, block, o)
         nets, prs, tables = self._seating_tables(actors, plist, o)
@@ -662,7 +682,8 @@ class VecSkillshotGame:
         bots = any(isinstance(a, ScriptedActor) for a in actors)
         res = self._match_launch("act_league", self._L.sk_env_act_league_bots if bots else self._L.sk_env_act_league,
                                  self._L.sk_env_act_league_bots_rec if bots else self._L.sk_env_act_league_rec, seats,
-                                 len(plist), block, start_obs, n_ticks, reward, o, resume, record)
+                                 len(plist), block, start_obs, n_ticks, reward, o, resume, record,
+                                 stats=self.new_stats(out=o.get("stats")) if stats else None)
         res.update(nets=nets, pairs=prs, tables=tables)
         if "record" in res:
             res["record"].pairs = [plist[p] for p in range(len(plist)) for _ in range(res["record"].per_block)]
@@ -814,6 +835,44 @@ class VecSkillshotGame:
             raise ValueError(f"out must be contiguous float32 [2, {self.n}, 2] on {self.device}")
         check(self._L.sk_env_bot_act(self._h, kind_code(kind), _ptr(a), self._stream()))
         return a
+
+    def _stats_fit(self):
+        if self.tick_limit * max(self.config.board_w, self.config.board_h) > 2 ** 31 - 1:
+            raise ValueError("the match statistics are int32: tick_limit * max(board_w, board_h) must fit in it")
+
+    def new_stats(self, out=None):
+        """A match-statistics buffer, int32 [SK_N_STATS + 2, 2, N]
+        (include/skillshot.h: plane _capi.STAT_NAMES.index(name), seat, game;
+        the last two planes carry the previous position between stats_tick
+        calls), initialised: zeros, `closest` at INT32_MAX, x_prev at
+        INT32_MIN.  out: a buffer to initialise again instead."""
+        self._stats_fit()
+        s = self._stats_buf(out) if out is not None else torch.empty((_capi.SK_N_STATS + 2, 2, self.n),
+                                                                     dtype=torch.int32, device=self.device)
+        s.zero_()
+        s[_capi.STAT_NAMES.index("closest")] = _capi.SK_STAT_FAR
+        s[_capi.SK_N_STATS] = _capi.SK_STAT_NO_PREV
+        return s
+
+    def _stats_buf(self, s):
+        shape = (_capi.SK_N_STATS + 2, 2, self.n)
+        if (not torch.is_tensor(s) or tuple(s.shape) != shape or s.dtype != torch.int32 or s.device != self.device or
+                not s.is_contiguous()):
+            raise ValueError(f"stats must be contiguous int32 {shape} on {self.device} (new_stats)")
+        return s
+
+    def stats_tick(self, stats, alive):
+        """One tick of the match statistics (sk_env_stats_tick,
+        csrc/sk_stats.hpp) from the current state, to be called before the
+        step: every game whose `alive` entry is set (the caller's loop test:
+        live and ticks < tick_limit) updates both seats' words of `stats`
+        (new_stats).  Both backends, the same integers from both; the
+        one-launch act_league(stats=True) tallies the same.  Advances
+        nothing."""
+        self._stats_fit()
+        mask = self._u8(alive)  # (held until the call has been issued: it may be a converted copy)
+        check(self._L.sk_env_stats_tick(self._h, _ptr(mask), _ptr(self._stats_buf(stats)), self._stream()))
+        return stats
 
     def rollout_random(self, n_ticks):
         """n_ticks random-policy ticks with auto-reset, one launch, state in registers."""
